@@ -1,19 +1,32 @@
 """Benchmark: DiffMM on Amazon-baby-shaped synthetic data, train users/s (+ full-rank eval users/s).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model diffmm|diffrec|genrecv1] [--no-legs]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--model diffmm|diffrec|genrecv1] [--no-legs]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and no more: setup, W warmup epochs, K timed epochs,
+the output dump when --dump-outputs is given, and the result line.  Everything else described below
+(the timed evaluation passes, the serial roofline epoch, the CPU baseline, the fp32-MFMA-only child
+run, the DiffRec / GenRecV1 legs, the GMR_DP_MODE=local measurement) runs only with --full.
+
+--dump-outputs DIR writes what the last timed epoch handed its caller as DIR/<name>.npy (float32;
+the losses float64): the epoch's BPR/contrastive loss, the diffusion losses, and every parameter the
+epoch updated (the rec slab and the denoisers' slabs, one file per parameter).  A parameter of more
+than DUMP_CAP elements is stored as a fixed seeded sample of its elements, so that the files stay
+under 64 MB in all.  The data, the initial weights and the device draws are seeded, so two runs with
+the same arguments start from identical inputs.
 
 One "step" = one full training epoch of the model's reference trainer.  For DiffMM (the headline,
 BASELINE.json) that is DiffMMTrainer._train_epoch (common/trainer.py:487-585): diffusion training
 of both denoisers over all users, the graph rebuild (p_sample + top-1 + normalised UI graphs) and
 the BPR/contrastive phase over all train interactions.  value = users/s = U * steps / wall (max
-over ranks); after the timed epochs full-rank evaluation passes over the valid split are timed
-as eval users/s.
+over ranks); with --full, full-rank evaluation passes over the valid split are timed after the
+timed epochs as eval users/s.
 Multi-GPU (N > 1): data parallelism over the ranks (gmr/dist.py) with the reference's global
 batch: each train_batch_size batch is split over the ranks, RCCL all-reduces the gradients, the
 rebuilt top-k edges are all-gathered; total work per epoch is fixed ("scaling": "strong").
 
-Roofline: after the timed region one more epoch runs with the side streams off (GMR_SERIAL
+Roofline (--full): after the timed region one more epoch runs with the side streams off (GMR_SERIAL
 semantics, gmr/kernels.py Streams.SERIAL) and every GEMM / SpMM / InfoNCE launch timed by HIP
 events on its stream; per kernel class achieved = algorithmic work (SURVEY.md 8d formulas) /
 summed duration.  `rocprofv3 --kernel-trace --stats` of `GMR_SERIAL=1 python bench.py` gives the
@@ -21,7 +34,7 @@ same per-kernel durations (profiles/).  Memory-side traffic and MFMA busy cycles
 rocprofv3 --pmc passes (scripts/pmc_collect.sh) recorded with the SHA-256 of the library they
 measured; a summary of another build is never used (traffic null then).
 
-With no --model the default run adds two legs measured in the same process: DiffRec on the
+With no --model a --full run adds two legs measured in the same process: DiffRec on the
 baby shape (config 2: train epoch + 100-step p_sample eval) and GenRecV1 on the TikTok shape
 with the fp16 MFMA scoring GEMM (config 5).
 """
@@ -288,8 +301,55 @@ def cpu_baseline(model, tl, reps=3):
                       f"{n_dif} diffusion + {n_dif} p_sample batches = {epoch:.1f}s/epoch"}
 
 
+DUMP_CAP = 2 * 1024 * 1024   # elements per dumped array (8 MB as float32) before sampling
+DUMP_LIMIT = 60 * 1024 * 1024  # bytes in all
+
+
+def collect_outputs(model, trainer, epoch_ret):
+    """What the last timed epoch handed its caller: its return value (the epoch's loss), the diffusion
+    losses it accumulated and the parameters it updated, as {name: device tensor or scalar}."""
+    out = {"train_loss": np.asarray([float(epoch_ret[0]) if isinstance(epoch_ret, tuple) else float(epoch_ret)],
+                                    dtype=np.float64)}
+    if getattr(trainer, "_dloss", None) is not None:
+        out["diffusion_loss_sums"] = trainer._dloss.detach().cpu().numpy().astype(np.float64)
+    slabs = [("rec" if len(model.optim_slabs()) == 1 else f"rec{i}", s) for i, s in enumerate(model.optim_slabs())]
+    for attr in ("denoise_model_image", "denoise_model_text"):
+        den = getattr(model, attr, None)
+        if den is not None and getattr(den, "slab", None) is not None and all(den.slab is not s for _, s in slabs):
+            slabs.append((attr, den.slab))
+    for prefix, slab in slabs:
+        for name in slab.layout:
+            out[f"{prefix}.{name}"] = slab.view(name)
+    return out
+
+
+def dump_outputs(dirname, outputs):
+    """DIR/<name>.npy per output; arrays over the cap as a fixed seeded sample of their elements."""
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_CAP
+    sizes = [int(v.numel()) for v in outputs.values() if torch.is_tensor(v)]  # the numpy entries are a few scalars
+    while sum(4 * min(n, cap) for n in sizes) > DUMP_LIMIT:
+        cap //= 2
+    total = 0
+    for name, v in outputs.items():
+        if torch.is_tensor(v):
+            flat = v.detach().contiguous().view(-1)
+            if flat.numel() > cap:
+                idx = np.sort(np.random.default_rng(20240229).choice(flat.numel(), cap, replace=False))
+                flat = flat[torch.as_tensor(idx, device=flat.device)]
+                arr = flat.float().cpu().numpy()
+            else:
+                arr = flat.float().cpu().numpy().reshape(tuple(v.shape))
+        else:
+            arr = v
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        total += arr.nbytes
+    log(f"dumped {len(outputs)} outputs ({total / 1e6:.1f} MB) to {dirname}")
+
+
 def run_workload(args, dist_on, barrier, max_over_ranks, with_cpu_baseline):
-    """Setup, warmup, timed epochs, eval passes and the serial roofline epoch of one model."""
+    """Setup, warmup and the timed epochs of one model; with --full the eval passes and the serial
+    roofline epoch as well."""
     from gmr import kernels as K
     cfg, ds, tr, tl, vl, model, trainer = setup(args)
     U = model.n_users
@@ -300,13 +360,25 @@ def run_workload(args, dist_on, barrier, max_over_ranks, with_cpu_baseline):
         log(f"warmup epoch {i}: {time.time() - t0:.3f}s")
     barrier()
     t0 = time.time()
+    ret = None
     for i in range(args.steps):
-        trainer._train_epoch(tl, args.warmup + i)
+        ret = trainer._train_epoch(tl, args.warmup + i)
         if getattr(trainer, "phase_ms", None):
             log("phases [ms]: diffusion %.2f, rebuild %.2f, bpr %.2f" % trainer.phase_ms)
     barrier()
     dt = max_over_ranks(time.time() - t0)
     train_ups = U * args.steps / dt
+    if getattr(args, "dump_outputs", None) and ret is not None and int(os.environ.get("RANK", "0")) == 0:
+        dump_outputs(args.dump_outputs, collect_outputs(model, trainer, ret))
+
+    out = {"model": MODELS[args.model], "shape": args.shape, "U": U, "I": model.n_items, "n_inter": tl.n_inter,
+           "train_users_per_s": round(train_ups, 1), "ms_per_step": round(1e3 * dt / args.steps, 2),
+           "global_batch": cfg["train_batch_size"], "eval_batch": cfg["eval_batch_size"]}
+    if not args.full:
+        del trainer, model
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        return out
 
     trainer.evaluate(vl)
     barrier()
@@ -342,11 +414,8 @@ def run_workload(args, dist_on, barrier, max_over_ranks, with_cpu_baseline):
         roof["_epoch"] = {"mfma_flop_per_epoch": mfma_flop, "serial_epoch_ms": round(serial_ms, 2),
                           "epoch_mfma_frac": round(mfma_flop / (dt / args.steps) / 1e12 / FP32_MFMA_PEAK_TFS, 4),
                           "note": "algorithmic GEMM + InfoNCE flop of one epoch / timed ms_per_step / fp32 MFMA peak"}
-    out = {"model": MODELS[args.model], "shape": args.shape, "U": U, "I": model.n_items, "n_inter": tl.n_inter,
-           "train_users_per_s": round(train_ups, 1), "ms_per_step": round(1e3 * dt / args.steps, 2),
-           "eval_users_per_s": round(eval_ups, 1), "eval_recall@20": res.get("recall@20"),
-           "eval_scoring_dtype": getattr(model, "scoring_dtype", "fp32"), "roofline_by_kernel": roof,
-           "global_batch": cfg["train_batch_size"], "eval_batch": cfg["eval_batch_size"]}
+    out.update({"eval_users_per_s": round(eval_ups, 1), "eval_recall@20": res.get("recall@20"),
+                "eval_scoring_dtype": getattr(model, "scoring_dtype", "fp32"), "roofline_by_kernel": roof})
     if with_cpu_baseline and args.model == "diffmm":
         try:
             out["cpu_baseline"] = cpu_baseline(model, tl)
@@ -392,7 +461,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--model", default=None, choices=sorted(MODELS), help="default: DiffMM headline + legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: timed eval passes, the serial roofline "
+                         "epoch, the CPU baseline, the fp32-MFMA-only child run, the DiffRec / GenRecV1 legs and "
+                         "(N > 1) the GMR_DP_MODE=local measurement; the --no-* options below trim a --full run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed (losses, updated parameters) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--model", default=None, choices=sorted(MODELS), help="default: DiffMM headline (+ legs with --full)")
     ap.add_argument("--shape", default=None, help="synthetic shape (default: baby; tiktok for GenRecV1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="headline only (no DiffRec / GenRecV1 legs)")
@@ -404,7 +480,7 @@ def main():
     args = ap.parse_args()
     # the DiffRec / GenRecV1 legs at N = 1 only: under data parallelism an exception in one rank's leg would leave
     # the others waiting in a collective, and the scaling line is the DiffMM headline's
-    legs = args.model is None and not args.no_legs and int(os.environ.get("WORLD_SIZE", "1")) == 1
+    legs = args.full and args.model is None and not args.no_legs and int(os.environ.get("WORLD_SIZE", "1")) == 1
     args.model = args.model or "diffmm"
     args.shape = args.shape or DEFAULT_SHAPE[args.model]
 
@@ -438,16 +514,17 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         return float(t.item())
 
-    head = run_workload(args, dist_on, barrier, max_over_ranks, world == 1 and not args.no_cpu_baseline)
+    head = run_workload(args, dist_on, barrier, max_over_ranks,
+                        args.full and world == 1 and not args.no_cpu_baseline)
     # N > 1: the headline keeps the reference's global batch (each 2,048-row batch split over the
     # GPUs); the opt-in GMR_DP_MODE=local schedule (each GPU takes whole batches: world x 2,048 rows
     # per optimiser step, 1 / world of the steps) is measured beside it under its own key
     dp_local = None
-    if dist_on and not args.no_dp_local and os.environ.get("GMR_DP_MODE", "global") != "local":
+    if args.full and dist_on and not args.no_dp_local and os.environ.get("GMR_DP_MODE", "global") != "local":
         os.environ["GMR_DP_MODE"] = "local"
         try:
             a3 = argparse.Namespace(**vars(args))
-            a3.no_probe = True
+            a3.no_probe, a3.dump_outputs = True, None
             r = run_workload(a3, dist_on, barrier, max_over_ranks, False)
             dp_local = {"value": r["train_users_per_s"], "unit": "users/s", "ms_per_step": r["ms_per_step"],
                         "global_batch": world * r["global_batch"], "eval_users_per_s": r["eval_users_per_s"],
@@ -465,7 +542,7 @@ def main():
     if legs and world == 1 and os.environ.get("GMR_GEMM_X6", "1") != "0":
         import subprocess
         env = dict(os.environ, GMR_GEMM_X6="0")
-        cmd = [sys.executable, os.path.abspath(__file__), "--model", "diffmm", "--no-legs", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--model", "diffmm", "--no-legs", "--no-cpu-baseline",
                "--no-probe", "--steps", str(args.steps), "--warmup", str(args.warmup), "--eval-passes", "1"]
         try:
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -479,6 +556,7 @@ def main():
         for key, m, shape, sd in (("diffrec", "diffrec", "baby", None), ("genrecv1_fp16", "genrecv1", "tiktok", "fp16")):
             a2 = argparse.Namespace(**vars(args))
             a2.model, a2.shape, a2.scoring_dtype, a2.steps, a2.warmup = m, shape, sd, max(2, args.steps), 1
+            a2.dump_outputs = None
             try:
                 r = run_workload(a2, dist_on, barrier, max_over_ranks, False)
                 dn, dobj = dominant(r.get("roofline_by_kernel"))
@@ -489,8 +567,6 @@ def main():
                 leg_out[key] = {"error": repr(e)}
 
     if rank == 0:
-        roof = head.pop("roofline_by_kernel")
-        dn, dobj = dominant(roof)
         line = {
             "metric": METRIC if args.model == "diffmm" else
             f"train users/sec + full-rank eval users/sec, {MODELS[args.model]} {args.shape}-shaped",
@@ -502,11 +578,15 @@ def main():
                                    f"items, {head['n_inter']} train interactions; step = {STEP_DESC[args.model]}",
                        "global_batch": head["global_batch"], "eval_batch": head["eval_batch"],
                        "parallelism": f"dp{world}"},
-            "eval_users_per_s": head["eval_users_per_s"], "eval_recall@20": head["eval_recall@20"],
-            "eval_scoring_dtype": head["eval_scoring_dtype"],
-            "roofline": dobj, "dominant_kernel": dn, "roofline_by_kernel": roof,
-            "lib_sha256": lib_sha256(),
+            "full": args.full,
         }
+        if args.full:
+            roof = head.pop("roofline_by_kernel")
+            dn, dobj = dominant(roof)
+            line.update({"eval_users_per_s": head["eval_users_per_s"], "eval_recall@20": head["eval_recall@20"],
+                         "eval_scoring_dtype": head["eval_scoring_dtype"],
+                         "roofline": dobj, "dominant_kernel": dn, "roofline_by_kernel": roof})
+        line["lib_sha256"] = lib_sha256()
         line["gemm_arith"] = (
             "fp32 operands and results; NT products (denoiser forward, p_sample) on the split-bf16 kernel: each fp32 "
             "operand split exactly into three bf16 terms, six bf16 MFMA products accumulated in fp32 (error vs fp64 "

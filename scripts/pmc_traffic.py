@@ -29,7 +29,7 @@ def load(path, counter):
 def main():
     fetch = load(sys.argv[1], "FETCH_SIZE")
     write = load(sys.argv[2], "WRITE_SIZE")
-    res = {"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE over `bench.py --steps 1 --warmup 1` (2 epochs + eval)",
+    res = {"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE over `bench.py --full --steps 1 --warmup 1` (2 epochs + eval)",
            "correction": "bytes = 2 * FETCH_SIZE_KB * 1024 + WRITE_SIZE_KB * 1024 (gfx950 FETCH_SIZE halving)"}
     for cls, names in CLASSES.items():
         f = sum(v for n, v in fetch if n in names) * 1024 * 2
