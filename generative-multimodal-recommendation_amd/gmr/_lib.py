@@ -183,6 +183,13 @@ SIGNATURES = {
     "gmr_xattn_bwd_f32": (I32, [I64, I32, I32, P, I64, P, I64, P, P, F32, P, P, P, I64, P]),
     "gmr_nce_pairs_f32": (I32, [I32, I64, I64, I64, P, P, P, I64, P, I64, P]),
     "gmr_nce_combine_f32": (I32, [I32, I64, I64, I64, P, P, P, I64, P, I64, P, I64, P]),
+    # FREEDOM
+    "gmr_frd_loss_fwd_bwd": (I32, [I32, I64, P, I64, P, I64, P, I64, P, P, P, F32, F32, P, P, P, I64, P]),
+    "gmr_frd_prune_keys": (I32, [I64, P, P, U64, U64, P, P]),
+    "gmr_frd_prune_workspace_ints": (I64, []),
+    "gmr_frd_prune_select": (I32, [I64, I64, P, P, P, P]),
+    "gmr_frd_knn_union_csr": (I32, [I64, I32, P, I64, F32, P, I64, F32, P, P, P, P, P, P, P]),
+    "gmr_frd_mean_fwd": (I32, [I64, I64, I32, P, P, P, I64, P, I64, P]),
 }
 
 _lib = None

@@ -732,6 +732,44 @@ int gmr_adam_f32(int64_t n, float* param, const float* grad, float* exp_avg, flo
                  float beta2, float eps, float weight_decay, float step_size, float bias_correction2_sqrt,
                  void* stream);
 
+/* ---------------------------------------------------------------- FREEDOM (models/freedom.py)
+ * calculate_loss (:189-210) in one call: loss = bpr(G) + reg_weight * (bpr(T) + bpr(V)) with
+ * bpr = -sum(logsigmoid(<u,p> - <u,n>)) * inv_norm over the B rows (the exact F.logsigmoid).  G is the
+ * propagated (n_users + I) x 64 table [ua; ia]; T / V are the I x 64 projected text / image tables (either may
+ * be NULL: that term and its columns are 0); the user row of all three terms is G[users[b]].  loss = [total,
+ * graph, text, image].  contrib (3B x 192, ldc): rows [users | pos | neg], columns [graph | text | image]; a user
+ * row carries the three terms' d/du in columns 0:64 and zeros after, so one gmr_scatter_sorted_f32 through the
+ * loader's BPR plan (key offsets [0, U, U]) gives the gradient of a (U + I) x 192 table [G | T | V].
+ * parts_ws: 3B doubles (per-row terms, summed in a fixed order).  All rows 16-byte aligned. */
+int gmr_frd_loss_fwd_bwd(int32_t B, int64_t n_users, const float* G, int64_t ldg, const float* T, int64_t ldt,
+                         const float* V, int64_t ldv, const int32_t* users, const int32_t* pos, const int32_t* neg,
+                         float reg_weight, float inv_norm, double* parts_ws, float* loss, float* contrib,
+                         int64_t ldc, void* stream);
+/* Degree-sensitive edge pruning (pre_epoch_processing, :128-143): torch.multinomial(w, m) without replacement
+ * as the m largest keys w_e / (-log u_e), u_e = Philox(seed, step, e) in (0, 1] or u[e] when u is given.
+ * gmr_frd_prune_select marks the m largest of the n_edges non-negative keys in keep (one byte per edge, exactly
+ * m set): radix histogram passes over the key bits find the m-th largest key, ties at it go to the lower edge
+ * index.  workspace: gmr_frd_prune_workspace_ints() ints.  m outside [0, n_edges] is an argument error. */
+int gmr_frd_prune_keys(int64_t n_edges, const float* w, const float* u, uint64_t seed, uint64_t step, float* keys,
+                       void* stream);
+int64_t gmr_frd_prune_workspace_ints(void);
+int gmr_frd_prune_select(int64_t n_edges, int64_t m, const float* keys, int32_t* workspace, uint8_t* keep,
+                         void* stream);
+/* mm_adj (:64-100): CSR of w_a A + w_b B for the binary top-k adjacencies A, B (n x k index lists, distinct per
+ * row), every entry weight / (k + 1e-7) evaluated as the reference does (pow(k + 1e-7, -0.5) squared, fp32).
+ * Columns ascending and distinct per row, an index in both lists gets the summed value; idx_b = NULL: w_a A
+ * alone.  stage_col / stage_val: n * 2k entries, count_ws: n ints; rowptr n + 1; col / val up to n * 2k entries
+ * (rowptr[n] are used). */
+int gmr_frd_knn_union_csr(int64_t n, int32_t k, const int32_t* idx_a, int64_t lda, float w_a, const int32_t* idx_b,
+                          int64_t ldb, float w_b, int32_t* stage_col, float* stage_val, int32_t* count_ws,
+                          int32_t* rowptr, int32_t* col, float* val, void* stream);
+/* forward (:164-178): out = (E_0 + ... + E_{n_layers-1}) / n_layers over n_rows x 64 tables (layers / ld_layers:
+ * host arrays), + h[r - n_users] on the rows from n_users (h may be NULL).  With one layer and no h it is a
+ * strided 64-column copy (the pre-fill of the backward's Horner chain). */
+#define GMR_FRD_MAX_LAYERS 8
+int gmr_frd_mean_fwd(int64_t n_rows, int64_t n_users, int32_t n_layers, const float* const* layers,
+                     const int64_t* ld_layers, const float* h, int64_t ldh, float* out, int64_t ldo, void* stream);
+
 /* (Round 5's native executor of a captured HIP graph, gmr_graph_exec_*, was removed in round 6: its replayed
  * step ran slower on the GPU than eager issue; the host tape of gmr/tape.py removes the Python issue cost and
  * keeps the eager streams and order.) */
