@@ -190,6 +190,23 @@ SIGNATURES = {
     "gmr_frd_prune_select": (I32, [I64, I64, P, P, P, P]),
     "gmr_frd_knn_union_csr": (I32, [I64, I32, P, I64, F32, P, I64, F32, P, P, P, P, P, P, P]),
     "gmr_frd_mean_fwd": (I32, [I64, I64, I32, P, P, P, I64, P, I64, P]),
+    # rectified-flow generator
+    "gmr_rf_param_floats": (I64, [I32, I32]),
+    "gmr_rf_tile_rows": (I32, []),
+    "gmr_rf_sample": (I32, [I64, I32, I32, I32, I32, P, I64, P, I64, P, P, I64, P]),
+    "gmr_rf_act_fwd": (I32, [I64, P, P, P, P, P, F32, P, P, P, P]),
+    "gmr_rf_act_parts_floats": (I64, [I64]),
+    "gmr_rf_act_bwd": (I32, [I64, P, P, P, P, P, F32, P, P, P, P, P, P, P]),
+    "gmr_rf_time_embed": (I32, [I64, P, P, P]),
+    "gmr_rf_interp": (I32, [I64, P, I64, P, P, P, P]),
+    "gmr_rf_head_fwd": (I32, [I64, P, P, P, I64, P, P, F32, P, P, P]),
+    "gmr_rf_head_bwd": (I32, [I64, P, P, I64, P, P, P, P, P]),
+    "gmr_rf_losses": (I32, [I64, P, I64, P, F32, P, P]),
+    "gmr_rf_infonce_sampled_fwd_bwd": (I32, [I32, I64, P, I64, P, I64, I64, P, I32, P, U64, U64, U64, F32, F32, P, P,
+                                             I64, P]),
+    "gmr_adamw_f32": (I32, [I64, P, P, P, P, F32, F32, F32, F32, F32, F32, P]),
+    "gmr_rf_randn": (I32, [I64, U64, U64, U64, P, P]),
+    "gmr_rf_rand": (I32, [I64, U64, U64, U64, P, P]),
 }
 
 _lib = None

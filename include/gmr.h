@@ -770,6 +770,65 @@ int gmr_frd_knn_union_csr(int64_t n, int32_t k, const int32_t* idx_a, int64_t ld
 int gmr_frd_mean_fwd(int64_t n_rows, int64_t n_users, int32_t n_layers, const float* const* layers,
                      const int64_t* ld_layers, const float* h, int64_t ldh, float* out, int64_t ldo, void* stream);
 
+/* ---------------------------------------------------------------- rectified-flow generator (models/rf_modules.py)
+ * SimpleVelocityNet with embedding_dim 64 and hidden_dim 128, condition_dim C in {64, 128}, L = rf_n_layers in 1..4.
+ * params: the net's named_parameters() order, every tensor dense and row-major (gmr_rf_param_floats(C, L) floats,
+ * 16-byte aligned): time_embed.1 {W 128x64, b}; condition_encoder {W 128xC, b, LN w, LN b}; input_proj {W 128x64, b,
+ * LN w, LN b}; L x res_blocks {W, b, LN w, LN b, W, b, LN w, LN b}; output_proj {W 128x128, b, LN w, LN b, W 64x128,
+ * b 64}.  LayerNorm: eps 1e-5, biased variance. */
+int64_t gmr_rf_param_floats(int32_t C, int32_t L); /* -1 outside the supported range */
+int32_t gmr_rf_tile_rows(void);                    /* rows a workgroup of gmr_rf_sample owns */
+/* generate() (:896-975): z <- z + net(z, i / n_steps, cond) / n_steps for i = 0 .. n_steps - 1 from z0, dropout and
+ * guidance off, the whole loop in one launch.  z0 N x 64 (ldz), cond N x C (ldc), out N x 64 (ldo); any N >= 1 (tail
+ * rows are masked).  A row's result does not depend on N or on the rows around it.  hidden != 128, C or L outside
+ * the range: GMR_ERR_ARG. */
+int gmr_rf_sample(int64_t N, int32_t hidden, int32_t C, int32_t L, int32_t n_steps, const float* z0, int64_t ldz,
+                  const float* cond, int64_t ldc, const float* params, float* out, int64_t ldo, void* stream);
+/* Rows of the training step over N x 128 contiguous tables:
+ *   out = drop(silu(LN(y) [+ res])) [+ add1] [+ add2],  drop(x) = mask ? x * keep_scale : 0
+ * ln_w == ln_b == NULL: no LayerNorm; res, mask, add1, add2 may be NULL.  Backward from dout = dL/dout: dy = dL/dy,
+ * dres (may be NULL) = the gradient of the pre-activation, which is the residual input's share; d_ln_w / d_ln_b are
+ * per-block partial sums (parts: gmr_rf_act_parts_floats(N) floats) added up in one fixed order. */
+int gmr_rf_act_fwd(int64_t N, const float* y, const float* ln_w, const float* ln_b, const float* res,
+                   const uint8_t* mask, float keep_scale, const float* add1, const float* add2, float* out,
+                   void* stream);
+int64_t gmr_rf_act_parts_floats(int64_t N);
+int gmr_rf_act_bwd(int64_t N, const float* y, const float* ln_w, const float* ln_b, const float* res,
+                   const uint8_t* mask, float keep_scale, const float* dout, float* dy, float* dres, float* parts,
+                   float* d_ln_w, float* d_ln_b, void* stream);
+/* SinusoidalPositionEmbedding(64) of t (N) -> N x 64 (:296-320) */
+int gmr_rf_time_embed(int64_t N, const float* t, float* out, void* stream);
+/* X_t = t X1 + (1 - t) X0 (:855); X1 N x 64 with ld1, the rest contiguous */
+int gmr_rf_interp(int64_t N, const float* X1, int64_t ld1, const float* X0, const float* t, float* Xt, void* stream);
+/* Head (:859-869): V (the net's output, in place) += (1 - t)^2 guidance_scale cosine_similarity_gradient(X_t, X1);
+ * row_parts[r] = sum_c (V - (X1 - X0))^2 in fp64; pred = X_t + (1 - t) V.
+ * Backward: dV = 2 (V - (X1 - X0)) / (64 N) + (1 - t) dpred. */
+int gmr_rf_head_fwd(int64_t N, float* V, const float* Xt, const float* X1, int64_t ld1, const float* X0,
+                    const float* t, float guidance_scale, float* pred, double* row_parts, void* stream);
+int gmr_rf_head_bwd(int64_t N, const float* V, const float* X1, int64_t ld1, const float* X0, const float* t,
+                    const float* dpred, float* dV, void* stream);
+/* out3 = [rf_loss = sum(row_parts) / (64 N), cl_loss = sum(cl_parts[0 : 2B]) / B, rf_loss + weight cl_loss] */
+int gmr_rf_losses(int64_t N, const double* row_parts, int64_t B, const double* cl_parts, float weight, float* out3,
+                  void* stream);
+/* _infonce_loss_interaction_based (:717-777) for B anchors idx[b] of one side (rows row_off + idx of pred and
+ * target, n rows on that side): n_neg negatives per anchor from neg (B x n_neg, side-relative) or, neg == NULL,
+ * drawn uniformly by Philox (seed, step, site; counter b n_neg + slot); a negative equal to the positive becomes
+ * (neg + 1) % n.  As the reference (:762, F.normalize over dim 1 of the (B, n_neg, 64) gather), a negative's column c
+ * is divided by the norm of column c over the anchor's n_neg negatives; the anchor and the positive are
+ * row-normalised.  parts[b] = -log(pos / (pos + sum neg)) in fp64; contrib[b] = coef * dloss_b / dpred[idx[b]] through
+ * the normalisation (the target side is constant), for gmr_scatter_sorted_f32. */
+int gmr_rf_infonce_sampled_fwd_bwd(int32_t B, int64_t n, const float* pred, int64_t ldp, const float* target,
+                                   int64_t ldt, int64_t row_off, const int32_t* idx, int32_t n_neg, const int32_t* neg,
+                                   uint64_t seed, uint64_t step, uint64_t site, float inv_temp, float coef,
+                                   double* parts, float* contrib, int64_t ldc, void* stream);
+/* torch.optim.AdamW: p <- p * decay_factor (= 1 - lr wd) first, then gmr_adam_f32's update without its L2 term */
+int gmr_adamw_f32(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
+                  float beta2, float eps, float decay_factor, float step_size, float bias_correction2_sqrt,
+                  void* stream);
+/* N(0, 1) / U[0, 1) draws from Philox (seed, step, site) */
+int gmr_rf_randn(int64_t n, uint64_t seed, uint64_t step, uint64_t site, float* out, void* stream);
+int gmr_rf_rand(int64_t n, uint64_t seed, uint64_t step, uint64_t site, float* out, void* stream);
+
 /* (Round 5's native executor of a captured HIP graph, gmr_graph_exec_*, was removed in round 6: its replayed
  * step ran slower on the GPU than eager issue; the host tape of gmr/tape.py removes the Python issue cost and
  * keeps the eager streams and order.) */
