@@ -461,12 +461,15 @@ __global__ __launch_bounds__(256) void rf_infonce_kernel(int64_t n, const float*
   if (lane == 0) rs[w] = se;
   __syncthreads();
   if (w != 0) return;
-  const float ttl = pos + (((rs[0] + rs[1]) + rs[2]) + rs[3]);
-  if (lane == 0) parts[b] = -(double)logf(pos / ttl);
+  // -log(pos / ttl) as log1p(sum / pos) and pos / ttl - 1 as -sum / ttl: with few or far negatives the sum is small
+  // against pos, and pos / ttl rounded next to 1 keeps only four digits of a loss of 1e-3 (and of k1)
+  const float nsum = ((rs[0] + rs[1]) + rs[2]) + rs[3];
+  const float ttl = pos + nsum;
+  if (lane == 0) parts[b] = (double)log1pf(nsum / pos);
   // d loss / d an = ((pos / ttl - 1) tp + sum_s (e_s / ttl) t_s) / temp, then through the normalisation
   const float4 gs = gmr::f4_add(gmr::f4_add(gmr::f4_add(rg[0][lane & 15], rg[1][lane & 15]), rg[2][lane & 15]),
                                 rg[3][lane & 15]);
-  const float k1 = pos / ttl - 1.f, k2 = 1.f / ttl;
+  const float k1 = -nsum / ttl, k2 = 1.f / ttl;
   const float4 gn = make_float4((k1 * tpn.x + gs.x * k2) * inv_temp, (k1 * tpn.y + gs.y * k2) * inv_temp,
                                 (k1 * tpn.z + gs.z * k2) * inv_temp, (k1 * tpn.w + gs.w * k2) * inv_temp);
   const float proj = group16_sum(dot4(an, gn));

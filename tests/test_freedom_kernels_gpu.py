@@ -141,16 +141,7 @@ def test_frd_select_bad_m():
 
 
 # ----------------------------------------------------------------------------- kNN union
-def _lists(kind, n, k, rng):
-    a = np.stack([rng.choice(n, k, replace=False) for _ in range(n)])
-    if kind == "identical":
-        return a, a.copy()
-    rest = [np.setdiff1d(np.arange(n), r) for r in a]
-    b = np.stack([rng.choice(r, k, replace=False) for r in rest])
-    if kind == "overlap":   # rows alternate: shares ceil(k / 2) entries with a / disjoint from a
-        h = (k + 1) // 2
-        b[::2, :h] = a[::2, k - h:]
-    return a, b
+from freedom_fixture import knn_lists as _lists  # noqa: E402  (shared with test_frd_kernels_shapes_gpu.py)
 
 
 @pytest.mark.parametrize("k", [1, 5])
