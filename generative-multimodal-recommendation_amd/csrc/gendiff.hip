@@ -727,7 +727,7 @@ extern "C" int gmr_dropout_f32(int64_t rows, int32_t D, int32_t group, const flo
 
 extern "C" int gmr_xattn_table_f32(int32_t L, int32_t D, int32_t nhead, const float* woc0, const float* bvc0,
                                    int64_t layer_stride, float p_keep, float* P, void* stream) {
-  GMR_ARG(woc0 && bvc0 && P && L > 0 && D > 0 && nhead > 0 && nhead <= 64 && D % nhead == 0, "bad args");
+  GMR_ARG(woc0 && bvc0 && P && L > 0 && D > 0 && nhead > 0 && nhead <= kXattnMaxHeads && D % nhead == 0, "bad args");
   GMR_ARG(p_keep > 0.f && p_keep <= 1.f, "p_keep in (0, 1]");
   const int64_t n = (int64_t)L * nhead * D;
   hipLaunchKernelGGL(xattn_table_kernel, dim3(gmr::grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, L, D, nhead,
@@ -739,7 +739,8 @@ extern "C" int gmr_xattn_table_f32(int32_t L, int32_t D, int32_t nhead, const fl
 extern "C" int gmr_xattn_fwd_f32(int64_t rows, int32_t D, int32_t nhead, const float* P, const float* bo, float p_keep,
                                  const uint8_t* mask_in, uint8_t* mask_out, int64_t ldm, uint64_t seed, uint64_t step,
                                  int64_t row0, float* CA, int64_t ldc, void* stream) {
-  GMR_ARG(P && bo && CA && rows > 0 && rows < (1ll << 31) && D > 0 && nhead > 0 && nhead <= 64 && D % nhead == 0 &&
+  GMR_ARG(P && bo && CA && rows > 0 && rows < (1ll << 31) && D > 0 && nhead > 0 && nhead <= kXattnMaxHeads &&
+              D % nhead == 0 &&
               ldm >= nhead && ldc >= D && row0 >= 0,
           "bad args");
   GMR_ARG(p_keep > 0.f && p_keep <= 1.f, "p_keep in (0, 1]");

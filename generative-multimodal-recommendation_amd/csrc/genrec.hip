@@ -81,13 +81,15 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(int64_t rows, const float
 __global__ void __launch_bounds__(1024) bn_finalize_kernel(int P, const double* __restrict__ part, int64_t rows,
                                                            float eps, float momentum, int train,
                                                            float* __restrict__ run_mean, float* __restrict__ run_var,
-                                                           float* __restrict__ mean_out, float* __restrict__ invstd_out) {
+                                                           float* __restrict__ mean_out, float* __restrict__ invstd_out,
+                                                           float* __restrict__ mean_lo) {
   __shared__ double rs[16][64], rq[16][64];
   const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
   if (!train) {
     if (g == 0) {
       mean_out[c] = run_mean[c];
       invstd_out[c] = 1.f / sqrtf(run_var[c] + eps);
+      mean_lo[c] = 0.f;
     }
     return;
   }
@@ -111,6 +113,7 @@ __global__ void __launch_bounds__(1024) bn_finalize_kernel(int P, const double* 
   if (var < 0.0) var = 0.0;
   mean_out[c] = (float)mean;
   invstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
+  mean_lo[c] = (float)(mean - (double)(float)mean);
   if (run_mean) {
     run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * (float)mean;
     run_var[c] = (1.f - momentum) * run_var[c] + momentum * (float)(rows > 1 ? var * n / (n - 1.0) : var);
@@ -118,11 +121,13 @@ __global__ void __launch_bounds__(1024) bn_finalize_kernel(int P, const double* 
 }
 
 // y = act(w (z - mean) invstd + b) [* keep * mscale]; post: 0 none, 1 out2 = rs * aux + y,
-// 2 out2 = aux * y, 3 rowdot[r] = <y_r, aux[0:64]>
+// 2 out2 = aux * y, 3 rowdot[r] = <y_r, aux[0:64]>.  mean_lo = the batch mean less its fp32 rounding: a column
+// whose mean is 1e4 standard deviations from zero loses 3e-4 of x_hat to that rounding alone
 __global__ void __launch_bounds__(256) bn_apply_kernel(int64_t rows, const float* __restrict__ z, int64_t ldz,
-                                                       const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                       const float* __restrict__ w, const float* __restrict__ b, int act,
-                                                       float slope, const uint8_t* __restrict__ mask, int64_t ldm,
+                                                       const float* __restrict__ mean, const float* __restrict__ mean_lo,
+                                                       const float* __restrict__ invstd, const float* __restrict__ w,
+                                                       const float* __restrict__ b, int act, float slope,
+                                                       const uint8_t* __restrict__ mask, int64_t ldm,
                                                        float mscale, float* __restrict__ y, int64_t ldy, int post,
                                                        const float* __restrict__ aux, int64_t ldaux,
                                                        const float* __restrict__ rs, float* __restrict__ out2,
@@ -133,10 +138,11 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(int64_t rows, const float
   const int c = (gid & 15) * 4;
   float4 a = f4(0, 0, 0, 0);
   if (ok) {
-    const float4 zz = ld4(z + r * ldz + c), mu = ld4(mean + c), is = ld4(invstd + c), ww = ld4(w + c), bb = ld4(b + c);
+    const float4 zz = ld4(z + r * ldz + c), mu = ld4(mean + c), lo = ld4(mean_lo + c), is = ld4(invstd + c),
+                 ww = ld4(w + c), bb = ld4(b + c);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float xh = (g4(zz, k) - g4(mu, k)) * g4(is, k);
+      const float xh = ((g4(zz, k) - g4(mu, k)) - g4(lo, k)) * g4(is, k);
       float v = act_f(act, xh * g4(ww, k) + g4(bb, k), slope);
       if (mask) v = mask[r * ldm + c + k] ? v * mscale : 0.f;
       s4(a, k, v);
@@ -171,7 +177,8 @@ struct BnBwdIn {
   const float* da; const float* v;
 };
 
-// upstream gradient of the BN output (pre-activation): dv, plus x_hat and the activation output
+// upstream gradient of the BN output (pre-activation): dv, plus x_hat and the layer's output (the kept, scaled
+// activation: what post 3's row dot multiplied by v)
 __device__ __forceinline__ void bn_bwd_elem(const BnBwdIn& p, int64_t r, int c, float4& dv, float4& xh, float4& av) {
   const float4 zz = ld4(p.z + r * p.ldz + c), mu = ld4(p.mean + c), is = ld4(p.invstd + c), ww = ld4(p.w + c),
                bb = ld4(p.b + c);
@@ -191,11 +198,15 @@ __device__ __forceinline__ void bn_bwd_elem(const BnBwdIn& p, int64_t r, int c, 
     const float x = (g4(zz, k) - g4(mu, k)) * g4(is, k);
     const float v = x * g4(ww, k) + g4(bb, k);
     const float a = act_f(p.act, v, p.slope);
-    float gg = g4(g, k);
-    if (p.mask) gg = p.mask[r * p.ldm + c + k] ? gg * p.mscale : 0.f;
+    float gg = g4(g, k), y = a;
+    if (p.mask) {
+      const bool kept = p.mask[r * p.ldm + c + k] != 0;
+      gg = kept ? gg * p.mscale : 0.f;
+      y = kept ? a * p.mscale : 0.f;
+    }
     s4(dv, k, gg * act_d(p.act, v, a, p.slope));
     s4(xh, k, x);
-    s4(av, k, a);
+    s4(av, k, y);
   }
 }
 
@@ -639,6 +650,10 @@ extern "C" int gmr_bn_fwd_f32(int64_t rows, const float* z, int64_t ldz, int32_t
   GMR_ARG(z && mean && invstd && w && b && parts, "null pointer");
   GMR_ARG(ldz % 4 == 0 && ldz >= 64, "z must be rows x 64 with ld % 4 == 0");
   GMR_ARG(act >= 0 && act <= 3 && post >= 0 && post <= 3, "bad act/post");
+  GMR_ARG(!y || (ldy % 4 == 0 && ldy >= 64), "y must be rows x 64 with ld % 4 == 0");
+  GMR_ARG(post == 0 || post == 3 || (ld_aux % 4 == 0 && ld_aux >= 64 && ld2 % 4 == 0 && ld2 >= 64),
+          "aux and out2 must be rows x 64 with ld % 4 == 0");
+  GMR_ARG(!keep || ld_keep >= 64, "keep must be rows x 64 bytes");
   GMR_ARG(train || (run_mean && run_var), "eval mode needs the running statistics");
   GMR_ARG(post == 0 || aux, "post op needs aux");
   GMR_ARG(post != 1 || (rs && out2), "post RES needs rs and out2");
@@ -647,15 +662,16 @@ extern "C" int gmr_bn_fwd_f32(int64_t rows, const float* z, int64_t ldz, int32_t
   GMR_ARG(y || post != 0, "nothing to write");
   hipStream_t st = (hipStream_t)stream;
   const int P = parts_for(rows);
+  float* mean_lo = reinterpret_cast<float*>(parts + (int64_t)128 * P);  // the statistics take 128 P of the 192 P doubles
   if (train) {
     hipLaunchKernelGGL(bn_stats_kernel, dim3(P), dim3(256), 0, st, rows, z, ldz, parts);
     GMR_LAUNCHED();
   }
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(1024), 0, st, P, parts, rows, eps, momentum, (int)train, run_mean,
-                     run_var, mean, invstd);
+                     run_var, mean, invstd, mean_lo);
   GMR_LAUNCHED();
-  hipLaunchKernelGGL(bn_apply_kernel, rows16(rows), dim3(256), 0, st, rows, z, ldz, mean, invstd, w, b, (int)act, slope,
-                     keep, ld_keep, keep_scale, y, ldy, (int)post, aux, ld_aux, rs, out2, ld2, rowdot);
+  hipLaunchKernelGGL(bn_apply_kernel, rows16(rows), dim3(256), 0, st, rows, z, ldz, mean, mean_lo, invstd, w, b, (int)act,
+                     slope, keep, ld_keep, keep_scale, y, ldy, (int)post, aux, ld_aux, rs, out2, ld2, rowdot);
   GMR_LAUNCHED();
   return GMR_OK;
 }
@@ -669,6 +685,12 @@ extern "C" int gmr_bn_bwd_f32(int64_t rows, const float* z, int64_t ldz, const f
   GR_CHECK_ROWS(rows);
   GMR_ARG(z && mean && invstd && w && b && parts && sums && dz, "null pointer");
   GMR_ARG((dy != nullptr) != (da != nullptr), "exactly one of dy / da");
+  GMR_ARG(ldz % 4 == 0 && ldz >= 64, "z must be rows x 64 with ld % 4 == 0");
+  GMR_ARG(lddz % 4 == 0 && lddz >= 64, "dz must be rows x 64 with ld % 4 == 0");
+  GMR_ARG(!dy || (lddy % 4 == 0 && lddy >= 64), "dy must be rows x 64 with ld % 4 == 0");
+  GMR_ARG(!(dy && mul) || (ld_mul % 4 == 0 && ld_mul >= 64), "mul must be rows x 64 with ld % 4 == 0");
+  GMR_ARG(act >= 0 && act <= 3, "bad act");
+  GMR_ARG(!keep || ld_keep >= 64, "keep must be rows x 64 bytes");
   GMR_ARG(!da || (v && dv), "rowdot backward needs v and dv");
   hipStream_t st = (hipStream_t)stream;
   BnBwdIn p{z, ldz, mean, invstd, w, b, (int)act, slope, keep, ld_keep, keep_scale, dy, lddy, mul, ld_mul, da, v};
@@ -745,6 +767,7 @@ extern "C" int gmr_dot64_f32(int64_t rows, const float* a, int64_t lda, const fl
                              float scale, float* out, int32_t accumulate, void* stream) {
   GR_CHECK_ROWS(rows);
   GMR_ARG(a && b && parts && out, "null pointer");
+  GMR_ARG(lda % 4 == 0 && lda >= 64 && ldb % 4 == 0 && ldb >= 64, "a and b must be rows x 64 with ld % 4 == 0");
   hipStream_t st = (hipStream_t)stream;
   const int P = gmr::grid_for(rows * 16, 256, 1024);
   hipLaunchKernelGGL(dot_part_kernel, dim3(P), dim3(256), 0, st, rows, a, lda, b, ldb, parts);

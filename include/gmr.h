@@ -526,7 +526,8 @@ int gmr_bn_fwd_f32(int64_t rows, const float* z, int64_t ldz, int32_t train, flo
                    int64_t ldy, int32_t post, const float* aux, int64_t ld_aux, const float* rs, float* out2,
                    int64_t ld2, float* rowdot, void* stream);
 /* backward of the above (train mode): upstream = dy (* mul) or, for post 3, da[r] * v[c]; writes
- * dz (accumulated if asked), dw/db (and dv for post 3; accumulated if asked); sums: 128 floats. */
+ * dz (accumulated if asked), dw/db (and dv for post 3, of the kept and scaled activation; accumulated if asked);
+ * sums: 128 floats.  Forward and backward read and write rows as float4: every ld a multiple of 4, at least 64. */
 int gmr_bn_bwd_f32(int64_t rows, const float* z, int64_t ldz, const float* mean, const float* invstd, const float* w,
                    const float* b, int32_t act, float slope, const uint8_t* keep, int64_t ld_keep, float keep_scale,
                    const float* dy, int64_t lddy, const float* mul, int64_t ld_mul, const float* da, const float* v,
