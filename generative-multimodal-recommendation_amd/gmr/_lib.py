@@ -207,6 +207,17 @@ SIGNATURES = {
     "gmr_adamw_f32": (I32, [I64, P, P, P, P, F32, F32, F32, F32, F32, F32, P]),
     "gmr_rf_randn": (I32, [I64, U64, U64, U64, P, P]),
     "gmr_rf_rand": (I32, [I64, U64, U64, U64, P, P]),
+    # LD4MRec C-Net rows
+    "gmr_ld4_film_fwd": (I32, [I64, I32, P, I64, P, P, P, I64, P, I64, F32, P, I64, P, P, P]),
+    "gmr_ld4_film_parts_floats": (I64, [I64, I32]),
+    "gmr_ld4_film_bwd": (I32, [I64, I32, P, I64, P, P, P, P, P, I64, P, I64, P, I64, P, I64, P, I64, I32, P, P, P, I32,
+                               P]),
+    "gmr_ld4_gelu_drop_fwd": (I32, [I64, I32, P, I64, F32, P, P, I64, U64, U64, U64, P, I64, P]),
+    "gmr_ld4_gelu_drop_bwd": (I32, [I64, I32, P, I64, P, I64, F32, P, I64, P, I64, P]),
+    "gmr_ld4_add_bias": (I32, [I64, I32, P, I64, P, P, I64, P]),
+    "gmr_ld4_loss_rows":(I32, [I32, I32, P, P, P, F32, P, I64, F32, P, I32, P]),
+    "gmr_ld4_history_ema": (I32, [I32, I32, P, P, P, P]),
+    "gmr_ld4_sample_t": (I32, [I32, I32, P, P, U64, U64, I64, P, P]),
 }
 
 _lib = None

@@ -830,6 +830,48 @@ int gmr_adamw_f32(int64_t n, float* param, const float* grad, float* exp_avg, fl
 int gmr_rf_randn(int64_t n, uint64_t seed, uint64_t step, uint64_t site, float* out, void* stream);
 int gmr_rf_rand(int64_t n, uint64_t seed, uint64_t step, uint64_t site, float* out, void* stream);
 
+/* ---------------------------------------------------------------- LD4MRec C-Net rows (csrc/ld4m.hip)
+ * ConditionalBlock (models/ld4mrec.py:57-87): n = LN(h) w + b, z = n (1 + s) + sh, h' = h + linear2(drop(gelu(
+ * linear1(z)))).  H: a multiple of 64 in 64..1024; every matrix has unit column stride, a row stride that is a
+ * multiple of 4 and a 16-byte aligned base (float4 loads, one 64-lane wave per row).
+ * film_fwd: z from h and the B x H modulation matrices s, sh (own strides); mean / rstd (rows each) saved.
+ * film_bwd, from dz: ds = dz n;  dsh = dz (dsh may be NULL or alias dz: no write);  dh (+)= LayerNorm backward of
+ * dz (1 + s);  dw / db (+)= through parts (gmr_ld4_film_parts_floats floats), added in block order. */
+int gmr_ld4_film_fwd(int64_t rows, int32_t H, const float* h, int64_t ldh, const float* w, const float* b,
+                     const float* s, int64_t lds, const float* sh, int64_t ldsh, float eps, float* z, int64_t ldz,
+                     float* mean, float* rstd, void* stream);
+int64_t gmr_ld4_film_parts_floats(int64_t rows, int32_t H);
+int gmr_ld4_film_bwd(int64_t rows, int32_t H, const float* h, int64_t ldh, const float* mean, const float* rstd,
+                     const float* w, const float* b, const float* s, int64_t lds, const float* dz, int64_t lddz,
+                     float* ds, int64_t ldds, float* dsh, int64_t lddsh, float* dh, int64_t lddh,
+                     int32_t accumulate_dh, float* parts, float* dw, float* db, int32_t accumulate_params,
+                     void* stream);
+/* y = gelu(x) keep / p_keep (exact erf GELU, inverted dropout).  keep[r][c] = mask_in[r][c] when mask_in is given,
+ * else drawn with gmr_keep_mask_u8's key (seed, step, ctr0 + r H + c) and recorded in mask_out (may be NULL);
+ * p_keep = 1 draws nothing and touches no mask.  Backward: dx = dy keep / p_keep gelu'(x) from the
+ * pre-activation x and the recorded mask (NULL at p_keep = 1); dx may alias dy. */
+int gmr_ld4_gelu_drop_fwd(int64_t rows, int32_t H, const float* x, int64_t ldx, float p_keep, const uint8_t* mask_in,
+                          uint8_t* mask_out, int64_t ldm, uint64_t seed, uint64_t step, uint64_t ctr0, float* y,
+                          int64_t ldy, void* stream);
+int gmr_ld4_gelu_drop_bwd(int64_t rows, int32_t H, const float* x, int64_t ldx, const uint8_t* mask, int64_t ldm,
+                          float p_keep, const float* dy, int64_t lddy, float* dx, int64_t lddx, void* stream);
+/* y = x + bias over rows x H (y may be x): the bias of item_proj after gmr_diff_sparse_pre's sum of weight rows */
+int gmr_ld4_add_bias(int64_t rows, int32_t H, const float* x, int64_t ldx, const float* bias, float* y, int64_t ldy,
+                     void* stream);
+/* loss_b = mean_I (pred_b - target_b)^2 (fp64), target = x0 (1 - gamma) + (1 - x0) gamma with x0 the train row of
+ * users[b] (user CSR); write_grad: pred <- 2 (pred - target) / I * grad_scale in place (ld4mrec.py:299-335). */
+int gmr_ld4_loss_rows(int32_t B, int32_t I, const int32_t* users, const int32_t* user_ptr, const int32_t* user_items,
+                      float gamma, float* pred, int64_t ld, float grad_scale, double* loss_out, int32_t write_grad,
+                      void* stream);
+/* hist[t_b] <- 0.9 hist[t_b] + 0.1 loss_b for b = 0 .. B-1 in that order, in the reference's fp32 arithmetic
+ * (ld4mrec.py:340-342); t_b < 0 skips the row.  T <= 1024. */
+int gmr_ld4_history_ema(int32_t B, int32_t T, const int32_t* t, const double* loss, float* hist, void* stream);
+/* t_b = searchsorted(cumsum(|hist| / sum |hist|), u_b, side = right) clamped to T - 1, the running sum in fp64
+ * (np.random.choice(T, B, p), ld4mrec.py:307-312).  u: B uniforms in [0, 1), or NULL: drawn from Philox keyed on
+ * (seed, step, row0 + b). */
+int gmr_ld4_sample_t(int32_t B, int32_t T, const float* hist, const float* u, uint64_t seed, uint64_t step,
+                     int64_t row0, int32_t* t, void* stream);
+
 /* (Round 5's native executor of a captured HIP graph, gmr_graph_exec_*, was removed in round 6: its replayed
  * step ran slower on the GPU than eager issue; the host tape of gmr/tape.py removes the Python issue cost and
  * keeps the eager streams and order.) */
