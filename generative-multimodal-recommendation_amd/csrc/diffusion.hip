@@ -654,6 +654,7 @@ extern "C" int gmr_diff_qsample(int32_t B, int32_t I, const int32_t* users, cons
   GMR_ARG(users && user_ptr && user_items && t && sqrt_ac && sqrt_1mac && x && B > 0 && I > 0 && row0 >= 0,
           "bad args");
   GMR_ARG(keep_prob > 0.f && keep_prob <= 1.f, "keep_prob must be in (0, 1]");
+  GMR_ARG(B == 1 || (ldx >= I && (!noise || ld_noise >= I) && (!keep || ld_keep >= I)), "row strides must be >= I");
   hipStream_t st = (hipStream_t)stream;
   const int64_t c4n = (I + 3) / 4;
   hipLaunchKernelGGL(qsample_dense_kernel, dim3(gmr::grid_for((int64_t)B * c4n, 256)), dim3(256), 0, st, B, I, t,
@@ -668,6 +669,7 @@ extern "C" int gmr_diff_qsample(int32_t B, int32_t I, const int32_t* users, cons
 extern "C" int gmr_diff_densify(int32_t B, int32_t I, const int32_t* users, const int32_t* user_ptr,
                                 const int32_t* user_items, float* x, int64_t ldx, void* stream) {
   GMR_ARG(user_ptr && user_items && x && B > 0 && I > 0, "bad args");
+  GMR_ARG(B == 1 || ldx >= I, "row stride must be >= I");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(densify_zero_kernel, dim3(gmr::grid_for((int64_t)B * I, 256)), dim3(256), 0, st, B, I, x, ldx);
   GMR_LAUNCHED();
@@ -713,6 +715,7 @@ extern "C" int gmr_diff_loss_rows(int32_t B, int32_t I, const int32_t* users, co
                                   float* out, int64_t ld, float grad_scale, double* mse_out, double* diff_out,
                                   double* loss_out, int32_t write_grad, void* stream) {
   GMR_ARG(users && user_ptr && user_items && t && wtab && out && mse_out && diff_out && B > 0 && I > 0, "bad args");
+  GMR_ARG(B == 1 || ld >= I, "row stride must be >= I");
   const size_t dyn = sizeof(uint32_t) * (size_t)((I + 31) / 32);
   GMR_ARG(dyn <= 60000, "item count too large for the LDS bitmap");
   hipLaunchKernelGGL(loss_rows_kernel, dim3(B), dim3(256), dyn, (hipStream_t)stream, B, I, users, user_ptr, user_items,
@@ -725,6 +728,7 @@ extern "C" int gmr_diff_gc_rows(int32_t B, const int32_t* users, const int32_t* 
                                 const float* item_embeds, int64_t ld_ie, const float* Z, int64_t ldz, float gscale,
                                 float* G, int64_t ldg, double* gc_out, void* stream) {
   GMR_ARG(users && user_ptr && user_items && item_embeds && Z && gc_out && B > 0, "bad args");
+  GMR_ARG(ld_ie >= 64 && (B == 1 || (ldz >= 64 && (!G || ldg >= 64))), "row strides must be >= 64");
   hipLaunchKernelGGL(gc_rows_kernel, dim3(gmr::grid_for(B, 4)), dim3(256), 0, (hipStream_t)stream, B, users, user_ptr,
                      user_items, item_embeds, ld_ie, Z, ldz, gscale, G, ldg, gc_out);
   GMR_LAUNCHED();
@@ -754,12 +758,13 @@ extern "C" int gmr_diff_time_bwd(int32_t T, int32_t E, int32_t H, const float* S
                                  float* d_emb_W, float* d_emb_b, int32_t accumulate, void* stream) {
   GMR_ARG(S && temb && emb && W1 && dW1 && db1 && d_emb_W && d_emb_b && T > 0 && H > 0, "bad args");
   GMR_ARG(E >= 1 && E <= 64, "time embedding size must be 1..64");
+  // before the first launch: a rejected call must not have accumulated into dW1 / db1
+  GMR_ARG((size_t)T * E * sizeof(float) <= 60000, "T * E too large for the LDS staging");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(time_bwd_h_kernel, dim3(gmr::grid_for((int64_t)H * E, 256)), dim3(256), 0, st, T, E, H, S, emb, dW1,
                      ld_w1,
                      col_off, db1, accumulate);
   GMR_LAUNCHED();
-  GMR_ARG((size_t)T * E * sizeof(float) <= 60000, "T * E too large for the LDS staging");
   if (T * E <= 64)
     hipLaunchKernelGGL(time_bwd_e_kernel<true>, dim3(1), dim3(1024), sizeof(float) * (size_t)T * E, st, T, E, H, S, W1,
                        ld_w1, col_off, temb, d_emb_W, d_emb_b, accumulate);

@@ -421,7 +421,9 @@ int gmr_permutation(int64_t n, uint64_t seed, uint64_t epoch, int32_t* out, void
  * dropout != 0; x0 rows come from the user's train items.  noise/keep may be NULL (Philox).
  * row0: index of row 0 inside the global batch — the Philox draws of a row depend on
  * (seed, step, row0 + b) only, so a batch split over data-parallel ranks draws what one
- * process drawing the whole batch would (trainer.py:491-527). */
+ * process drawing the whole batch would (trainer.py:491-527).
+ * Row strides (ldx, ld_noise / ld_keep of a non-NULL buffer, ld of the loss rows, the three of gc_rows) below the
+ * row width are rejected when B > 1; every argument check returns before the first launch. */
 int gmr_diff_sample_t(int32_t B, int32_t T, uint64_t seed, uint64_t step, int64_t row0, int32_t* t, void* stream);
 int gmr_diff_qsample(int32_t B, int32_t I, const int32_t* users, const int32_t* user_ptr, const int32_t* user_items,
                      const int32_t* t, const float* sqrt_ac, const float* sqrt_1mac, const float* noise,

@@ -64,8 +64,9 @@ def _film_fp32_error(c, H, z_ref):
     return float(np.abs(z.double().numpy() - z_ref).max())
 
 
-@pytest.mark.parametrize("H", [64, 256, 320])
-@pytest.mark.parametrize("rows", [1, 5, 67, 300])
+# H 576 fills a lane's third float4 for lanes 0..15 only, 1024 all four; 8 rows are one film_bwd workgroup, 9 one more
+@pytest.mark.parametrize("H", [64, 256, 320, 576, 1024])
+@pytest.mark.parametrize("rows", [1, 5, 8, 9, 67, 300])
 def test_film_fwd_bwd(rows, H):
     from gmr import _lib
     c = _film_case(rows, H)
@@ -126,6 +127,26 @@ def test_film_rejects_width():
               _ptr(v), _ptr(v), _stream())
 
 
+# ----------------------------------------------------------------------------- add_bias
+@pytest.mark.parametrize("H", [64, 1024])
+def test_add_bias(H):
+    """y = x + bias is one IEEE add per entry: bit-equal to fp32 numpy, out of place and with y == x."""
+    rows = 37
+    rng = np.random.default_rng(H)
+    x = rng.standard_normal((rows, H)).astype(np.float32)
+    bias = rng.standard_normal(H).astype(np.float32)
+    want = x + bias[None, :]
+    d_x, d_b = _strided(x, 8), dev(bias)
+    y = _strided(np.full((rows, H), np.nan, np.float32), 4)
+    _call("gmr_ld4_add_bias", rows, H, _ptr(d_x), d_x.stride(0), _ptr(d_b), _ptr(y), y.stride(0), _stream())
+    np.testing.assert_array_equal(y.cpu().numpy(), want)
+    np.testing.assert_array_equal(d_x.cpu().numpy(), x)
+    _call("gmr_ld4_add_bias", rows, H, _ptr(d_x), d_x.stride(0), _ptr(d_b), _ptr(d_x), d_x.stride(0), _stream())
+    np.testing.assert_array_equal(d_x.cpu().numpy(), want)
+    assert float(y._base[:, H:].min()) == 7.0 and float(d_x._base[:, H:].min()) == 7.0  # pads untouched
+    assert float(y._base[:, H:].max()) == 7.0 and float(d_x._base[:, H:].max()) == 7.0
+
+
 # ----------------------------------------------------------------------------- GELU + dropout
 def _gelu_fwd(x, p_keep, mask_in, mask_out, key=(11, 4, 1000), y=None):
     rows, H = x.shape
@@ -136,11 +157,22 @@ def _gelu_fwd(x, p_keep, mask_in, mask_out, key=(11, 4, 1000), y=None):
 
 
 def test_gelu_drop():
-    rows, H = 300, 256
+    _gelu_drop_case(300, 256, "cpu")
+
+
+# 4099 x 1024 is 4099 blocks of 256 float4; the launch is capped at 16384 blocks, which 16387 x 1024 passes, so every
+# thread there takes a second grid stride.  For these two shapes alone the fp64 reference is evaluated on the device.
+@pytest.mark.parametrize("rows", [4099, 16387])
+def test_gelu_drop_large(rows):
+    assert 16387 * (1024 // 4) > 16384 * 256
+    _gelu_drop_case(rows, 1024, DEV)
+
+
+def _gelu_drop_case(rows, H, ref_dev):
     rng = np.random.default_rng(8)
     x = dev((1.5 * rng.standard_normal((rows, H))).astype(np.float32))
-    x64 = x.double().cpu()
-    gelu = torch.nn.functional.gelu(x64).numpy()
+    x64 = x.double().to(ref_dev)
+    gelu = torch.nn.functional.gelu(x64).cpu().numpy()
     # p_keep = 1: exact GELU, no mask touched
     # rtol 1e-5, and where (1 + erf) cancels for negative x (fp32 error eps32 |x| / 2, far above 1e-5 of a tiny
     # result) twice the largest error of fp32 torch's own exact GELU against fp64
@@ -170,8 +202,8 @@ def test_gelu_drop():
         xr = x64.clone().requires_grad_(True)
         out = torch.nn.functional.gelu(xr)
         if m is not None:
-            out = out * m.cpu().double() / float(np.float32(0.9))
-        ref = torch.autograd.grad(out, xr, dy.double().cpu())[0].numpy()
+            out = out * m.to(ref_dev).double() / float(np.float32(0.9))
+        ref = torch.autograd.grad(out, xr, dy.double().to(ref_dev))[0].cpu().numpy()
         dx = torch.empty_like(x)
         _call("gmr_ld4_gelu_drop_bwd", rows, H, _ptr(x), x.stride(0), _ptr(m), H, pk, _ptr(dy), dy.stride(0), _ptr(dx),
               dx.stride(0), _stream())
@@ -185,11 +217,14 @@ def test_loss_rows(I):
     U, B, gamma = 23, 19, 0.1
     deg = rng.integers(1, min(I, 30), U)
     deg[4] = 0                                   # a user with an empty history
+    if I > 300:
+        deg[7] = 300                             # past one 256-thread pass of the bitmap fill
     items = [np.sort(rng.choice(I, d, replace=False)) for d in deg]
     uptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int32)
     uitems = np.concatenate(items).astype(np.int32)
     users = rng.integers(0, U, B).astype(np.int32)
     users[0], users[1], users[2] = 4, 9, 9       # the empty user; a user repeated in the batch
+    users[3] = 7
     pred = rng.standard_normal((B, I)).astype(np.float32)
     X = np.zeros((U, I))
     for u_, it in enumerate(items):
@@ -254,8 +289,16 @@ def _sample(hist, u=None, B=None, key=(5, 9), row0=0):
 
 
 def test_sample_t_injected():
+    _sample_t_injected_case(100)
+
+
+@pytest.mark.parametrize("T", [1, 1024])  # one bin; the largest table
+def test_sample_t_injected_other_T(T):
+    _sample_t_injected_case(T)
+
+
+def _sample_t_injected_case(T):
     rng = np.random.default_rng(6)
-    T = 100
     hist = rng.uniform(0.2, 3.0, T).astype(np.float32)
     hist[::7] *= -1                              # |hist| is what counts
     a = np.abs(hist.astype(np.float64))
@@ -283,3 +326,27 @@ def test_sample_t_philox():
     assert not np.array_equal(_sample(hist, B=B, key=(5, 10)), t)
     halves = np.concatenate([_sample(hist, B=2048), _sample(hist, B=2048, row0=2048)])
     np.testing.assert_array_equal(halves, t)                             # keyed by the global row
+
+
+def _sample_replica(hist, B, key, row0):
+    """The kernel's Philox branch on the CPU: 24-bit u in [0, 1), the fp64 cdf summed in order, t = #{k: cdf_k <= u}
+    clamped; and the smallest distance of any u from an edge."""
+    import philox_ref
+    T = len(hist)
+    a = np.abs(hist.astype(np.float64))
+    tot = np.cumsum(a)[-1]  # np.cumsum adds in order
+    cdf = np.cumsum(a / tot)
+    w = philox_ref.philox(key[0] ^ 0xA5A5A5A5, key[1], row0 + np.arange(B, dtype=np.uint64))
+    u = (w[:, 0] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+    t = np.minimum(np.searchsorted(cdf, u, side="right"), T - 1).astype(np.int32)
+    return t, float(np.abs(u[:, None] - cdf[None, :]).min())
+
+
+@pytest.mark.parametrize("T", [1, 100, 1024])
+def test_sample_t_philox_replica(T):
+    B, key, row0 = 4096, (5, 9), 123
+    hist = np.random.default_rng(T).uniform(0.2, 3.0, T).astype(np.float32)
+    hist[::5] *= -1
+    want, gap = _sample_replica(hist, B, key, row0)
+    assert T == 1 or gap > 1e-12   # decided on the CPU: a last-bit difference of the device's cdf moves no draw
+    np.testing.assert_array_equal(_sample(hist, B=B, key=key, row0=row0), want)
