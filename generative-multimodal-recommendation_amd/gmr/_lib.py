@@ -218,6 +218,15 @@ SIGNATURES = {
     "gmr_ld4_loss_rows":(I32, [I32, I32, P, P, P, F32, P, I64, F32, P, I32, P]),
     "gmr_ld4_history_ema": (I32, [I32, I32, P, P, P, P]),
     "gmr_ld4_sample_t": (I32, [I32, I32, P, P, U64, U64, I64, P, P]),
+    # DDRM
+    "gmr_ddrm_tile_rows": (I32, []),
+    "gmr_ddrm_denoise_fwd": (I32, [I64, I32, I32, I64, P, I64, P, P, I64, P, P, P, P, P, I64, I32, P, I64, U64, U64,
+                                   U64, P, P, P, P, P, I64, P, I64, P, I64, P, I64, P, P]),
+    "gmr_ddrm_chain": (I32, [I64, I32, I32, I32, I64, P, I64, P, I64, F32, F32, P, I64, P, P, P, P, P, P, P, P, P,
+                             U64, U64, U64, P, I64, P]),
+    "gmr_ddrm_loss_fwd_bwd": (I32, [I32, I64, P, I64, P, P, P, P, I64, P, I64, P, P, P, F32, F32, F32, F32, P, P, P,
+                                    I64, P, P, P]),
+    "gmr_ddrm_input_bwd": (I32, [I64, P, P, I64, P, P, P, P, I64, P]),
 }
 
 _lib = None

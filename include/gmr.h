@@ -874,6 +874,48 @@ int gmr_ld4_history_ema(int32_t B, int32_t T, const int32_t* t, const double* lo
 int gmr_ld4_sample_t(int32_t B, int32_t T, const float* hist, const float* u, uint64_t seed, uint64_t step,
                      int64_t row0, int32_t* t, void* stream);
 
+/* ---------------------------------------------------------------- DDRM (models/ddrm.py; csrc/ddrm.hip)
+ * The conditional denoiser out = W2 tanh(W1 [x | emb_layer(temb(t)) | cond] + b1) + b2 on 64-wide rows, hidden width
+ * H (a multiple of 4 in 4..1024).  W1: H x 192 (row stride 192), W2: 64 x H (row stride H), both 16-byte aligned.
+ * TB (T x H, row stride H) is the folded time table TB[t] = W1[:, 64:128] emb_layer(temb(t)) + b1, built by the caller.
+ * A row's result depends on its inputs and its global row number row_off + r only (not on N or its neighbours). */
+int32_t gmr_ddrm_tile_rows(void);
+/* One training forward of one denoiser over N rows: x0 = X[idx_x[r]] and cond = C[idx_c[r]] (idx NULL: row r),
+ * x_t = sqrt_ac[t_r] x0 + sqrt_1mac[t_r] noise_r, xd = dropout_0.5(x_t), h = tanh(.), out, rowmse_r = mean_64 (x0 -
+ * out)^2.  noise (N x 64, ldn) or NULL: Philox (seed, step, site; row row_off + r).  drop_mode 0: no dropout; 1: the
+ * keep bytes `keep` (N x 64, ldk); 2: drawn from Philox (site + 1) and written to keep_out.  xd, keep_out, h, rowmse
+ * may be NULL. */
+int gmr_ddrm_denoise_fwd(int64_t N, int32_t H, int32_t T, int64_t row_off, const float* X, int64_t ldx,
+                         const int32_t* idx_x, const float* C, int64_t ldc, const int32_t* idx_c, const int32_t* t,
+                         const float* sqrt_ac, const float* sqrt_1mac, const float* noise, int64_t ldn,
+                         int32_t drop_mode, const uint8_t* keep, int64_t ldk, uint64_t seed, uint64_t step,
+                         uint64_t site, const float* W1, const float* TB, const float* W2, const float* b2, float* out,
+                         int64_t ldo, float* xd, int64_t ldxd, uint8_t* keep_out, int64_t ldko, float* h, int64_t ldh,
+                         float* rowmse, void* stream);
+/* The reverse chain of full_sort_predict in one launch, eval mode: x = xs (noise0 != NULL: qa xs + qb noise0), then
+ * for i = S-1..0: x <- c1[i] net(x, cond, i) + c2[i] x, + sigma[i] noise_i where i != 0 when sigma != NULL (noise_i =
+ * step_noise[i] of an S x N x 64 array, or Philox keyed on (seed, step, site; (row_off + r) T + i)).  S = 0 copies. */
+int gmr_ddrm_chain(int64_t N, int32_t H, int32_t T, int32_t S, int64_t row_off, const float* xs, int64_t ldx,
+                   const float* noise0, int64_t ldn0, float qa, float qb, const float* C, int64_t ldc,
+                   const int32_t* idx_c, const float* W1, const float* TB, const float* W2, const float* b2,
+                   const float* c1, const float* c2, const float* sigma, const float* step_noise, uint64_t seed,
+                   uint64_t step, uint64_t site, float* out, int64_t ldo, void* stream);
+/* calculate_loss's row loss (:405-433) with its backward.  G: the propagated (n_users + I) x 64 table; with u, p, n
+ * the rows of users / pos / neg: w = sigmoid(<u,p>)^beta (no gradient), sp = softplus(<u,n> - <u,p>), rec = (mse_u +
+ * mse_i) / 2, loss_b = w ((1 - alpha) (sp + reg_weight reg[0]) + alpha rec).  terms (4 x B): [w | sp | rec | loss_b];
+ * loss[0] = sum(loss_b) inv_norm (fp64, fixed order), loss[1] = (1 - alpha) reg_weight sum(w) inv_norm, the
+ * coefficient of reg, loss[2] = loss[1] inv_norm (3 floats).  contrib (3B x 64, ldc): rows [users | pos | neg] for gmr_scatter_sorted_f32 (scores and the
+ * recon targets); dout_u, dout_i (B x 64 dense): d loss / d the denoiser outputs. */
+int gmr_ddrm_loss_fwd_bwd(int32_t B, int64_t n_users, const float* G, int64_t ldg, const int32_t* users,
+                          const int32_t* pos, const int32_t* neg, const float* out_u, int64_t ldou, const float* out_i,
+                          int64_t ldoi, const float* mse_u, const float* mse_i, const float* reg, float alpha,
+                          float beta, float reg_weight, float inv_norm, float* terms, float* loss, float* contrib,
+                          int64_t ldc, float* dout_u, float* dout_i, void* stream);
+/* dst[r] += sqrt_ac[t_r] (keep ? 2 : 0) dxd[r] + dcond[r] over N x 64 rows (dxd, dcond dense; keep NULL: no
+ * dropout): the gradient of a gathered row through q_sample and through the other model's cond columns */
+int gmr_ddrm_input_bwd(int64_t N, const float* dxd, const uint8_t* keep, int64_t ldk, const int32_t* t,
+                       const float* sqrt_ac, const float* dcond, float* dst, int64_t ldd, void* stream);
+
 /* (Round 5's native executor of a captured HIP graph, gmr_graph_exec_*, was removed in round 6: its replayed
  * step ran slower on the GPU than eager issue; the host tape of gmr/tape.py removes the Python issue cost and
  * keeps the eager streams and order.) */
