@@ -227,6 +227,12 @@ SIGNATURES = {
     "gmr_ddrm_loss_fwd_bwd": (I32, [I32, I64, P, I64, P, P, P, P, I64, P, I64, P, P, P, F32, F32, F32, F32, P, P, P,
                                     I64, P, P, P]),
     "gmr_ddrm_input_bwd": (I32, [I64, P, P, I64, P, P, P, P, I64, P]),
+    # BM3
+    "gmr_bm3_tile_rows": (I32, []),
+    "gmr_bm3_loss_fwd_bwd": (I32, [I32, I64, P, I64, P, I64, P, I64, P, P, P, I64, P, F32, F32, F32, I32, P, P, P, P,
+                                   I64, U64, U64, U64, P, P, P, P, I64, P, P, I64, P, P, P]),
+    "gmr_bm3_loss_reduce": (I32, [I32, P, P, I32, I32, F32, F32, F32, I64, P, P]),
+    "gmr_bm3_reg_bwd": (I32, [I64, I64, P, P, I64, P, I64, P]),
 }
 
 _lib = None

@@ -916,6 +916,37 @@ int gmr_ddrm_loss_fwd_bwd(int32_t B, int64_t n_users, const float* G, int64_t ld
 int gmr_ddrm_input_bwd(int64_t N, const float* dxd, const uint8_t* keep, int64_t ldk, const int32_t* t,
                        const float* sqrt_ac, const float* dcond, float* dst, int64_t ldd, void* stream);
 
+/* ---------------------------------------------------------------- BM3 (models/bm3.py; csrc/bm3.hip)
+ * calculate_loss's six cosine terms (:121-147) with their backward in one launch.  G: the (n_users + I) x 64 table
+ * [ua; ib]; T / V: the I x 64 projected text / image tables (either may be NULL: its stream's outputs are 0); every
+ * table has its own row stride (16-byte aligned rows).  Streams u = G[users], i = G[n_users + items], t = T[items],
+ * v = V[items]; P(x) = x Wp^T + bp (Wp 64 x 64, row stride ldw); targets drop(x) = keep x / (1 - p), no gradient.
+ * drop_mode 0: no dropout; 1: the keep bytes of the batch rows (B x 64 per present stream, ldk); 2: drawn by Philox
+ * keyed on (seed + (site + stream) 0x9E3779B97F4A7C15, step, table row id * 16 + column / 4), a column kept when
+ * (word >> 8) 2^-24 < 1 - p, and written to the keep_out arrays that are not NULL (ldko).
+ *   terms   (6 x B)      the cosines [ui | iu | t | v | tv | vt]
+ *   contrib (2B x 192)   rows 0..B-1 [dx_u | 0 | 0], rows B..2B-1 [dx_i | dx_t | dx_v], dx = d_on Wp, every element
+ *                        written: one gmr_scatter_sorted_f32 through the plan of keys [users | n_users + items]
+ *   xg, don (4B x 64)    the gathered inputs and d loss / d P(x), stacked by stream: dWp = don^T xg, dbp = colsum(don)
+ * d_on carries inv_norm (the modal streams also cl_weight, their two terms summed). */
+int32_t gmr_bm3_tile_rows(void);
+int gmr_bm3_loss_fwd_bwd(int32_t B, int64_t n_users, const float* G, int64_t ldg, const float* T, int64_t ldt,
+                         const float* V, int64_t ldv, const int32_t* users, const int32_t* items, const float* Wp,
+                         int64_t ldw, const float* bp, float p, float cl_weight, float inv_norm, int32_t drop_mode,
+                         const uint8_t* keep_u, const uint8_t* keep_i, const uint8_t* keep_t, const uint8_t* keep_v,
+                         int64_t ldk, uint64_t seed, uint64_t step, uint64_t site, uint8_t* keep_out_u,
+                         uint8_t* keep_out_i, uint8_t* keep_out_t, uint8_t* keep_out_v, int64_t ldko, float* terms,
+                         float* contrib, int64_t ldc, float* xg, float* don, void* stream);
+/* loss (10 floats) = [total, ui, iu, t, v, tv, vt, reg, cu, ci]: term = 1 - sum(cos) inv_norm (0 for an absent
+ * modality), reg = (sqrt(sqnorms[0]) + sqrt(sqnorms[1])) / n_items, total = ui + iu + reg_weight reg + cl_weight (t +
+ * v + tv + vt); cu, ci = reg_weight / (n_items sqrt(sqnorms[k])) (0 for a zero norm), the coefficients of
+ * gmr_bm3_reg_bwd.  Fixed-order fp64 sums; sqnorms: the squared Frobenius norms of ua and ib on the device. */
+int gmr_bm3_loss_reduce(int32_t B, const float* terms, const float* sqnorms, int32_t has_t, int32_t has_v,
+                        float reg_weight, float cl_weight, float inv_norm, int64_t n_items, float* loss, void* stream);
+/* dG[r] += coef[r < n_users ? 0 : 1] G[r] over n_rows x 64 (coef: two device floats) */
+int gmr_bm3_reg_bwd(int64_t n_rows, int64_t n_users, const float* coef, const float* G, int64_t ldg, float* dG,
+                    int64_t ldd, void* stream);
+
 /* (Round 5's native executor of a captured HIP graph, gmr_graph_exec_*, was removed in round 6: its replayed
  * step ran slower on the GPU than eager issue; the host tape of gmr/tape.py removes the Python issue cost and
  * keeps the eager streams and order.) */
