@@ -6,7 +6,7 @@
 //                                    v_mfma_f32_32x32x2_f32
 //   gmr_rf_act_fwd / gmr_rf_act_bwd  [LayerNorm] + SiLU [+ dropout mask] [+ residual] rows of the training step,
 //                                    LN weight / bias gradients as fixed-order column reductions (no float atomics)
-//   gmr_rf_time_embed, gmr_rf_interp, gmr_rf_head_fwd / _bwd, gmr_rf_losses
+//   gmr_rf_time_embed, gmr_rf_interp, gmr_rf_head_fwd / _prior_fwd / _bwd, gmr_rf_losses
 //   gmr_rf_infonce_sampled_fwd_bwd   sampled InfoNCE of the predicted end points against the detached targets
 //   gmr_adamw_f32                    Adam with decoupled decay (torch.optim.AdamW)
 //   gmr_rf_randn / gmr_rf_rand       Philox draws keyed on (seed, step, site)
@@ -320,12 +320,16 @@ __global__ void rf_interp_kernel(int64_t N, const float* __restrict__ X1, int64_
   Xt[i] = tt * X1[row * ld1 + c] + (1.f - tt) * X0[i];
 }
 
-// one wave per row, lane = column: v += (1 - t)^2 scale cos_grad(Xt, X1); squared error to parts; pred
+// one wave per row, lane = column: v += (1 - t)^2 scale cos_grad(Xt, X1); squared error to parts; pred.  PRIOR: the
+// user-prior term (1 - t)^2 pscale prior is added first, as the reference orders the two guidance terms
+template <bool PRIOR>
 __global__ __launch_bounds__(256) void rf_head_fwd_kernel(int64_t N, float* __restrict__ V,
                                                           const float* __restrict__ Xt, const float* __restrict__ X1,
                                                           int64_t ld1, const float* __restrict__ X0,
-                                                          const float* __restrict__ t, float gscale,
-                                                          float* __restrict__ pred, double* __restrict__ parts) {
+                                                          const float* __restrict__ t,
+                                                          const float* __restrict__ prior, int64_t ldp, float pscale,
+                                                          float gscale, float* __restrict__ pred,
+                                                          double* __restrict__ parts) {
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;
   const int lane = threadIdx.x & 63;
@@ -337,7 +341,9 @@ __global__ __launch_bounds__(256) void rf_head_fwd_kernel(int64_t N, float* __re
   const float ntc = fmaxf(nt, 1e-8f);
   const float grad = (x1 / fmaxf(n1, 1e-12f)) / ntc - (xt / fmaxf(nt, 1e-12f)) * cs / ntc;
   const float lam = (1.f - tt) * (1.f - tt);
-  const float v = V[o] + lam * gscale * grad;
+  float v = V[o];
+  if (PRIOR) v = v + lam * pscale * prior[row * ldp + lane];
+  v = v + lam * gscale * grad;
   V[o] = v;
   const float e = v - (x1 - x0);
   const double sq = gmr::wave_sum_d((double)e * (double)e);
@@ -592,8 +598,20 @@ extern "C" int gmr_rf_interp(int64_t N, const float* X1, int64_t ld1, const floa
 extern "C" int gmr_rf_head_fwd(int64_t N, float* V, const float* Xt, const float* X1, int64_t ld1, const float* X0,
                                const float* t, float guidance_scale, float* pred, double* row_parts, void* stream) {
   GMR_ARG(N >= 1 && V && Xt && X1 && X0 && t && pred && row_parts && ld1 >= D, "bad args");
-  hipLaunchKernelGGL(rf_head_fwd_kernel, dim3(gmr::grid_for(N, 4)), dim3(256), 0, (hipStream_t)stream, N, V, Xt, X1,
-                     ld1, X0, t, guidance_scale, pred, row_parts);
+  hipLaunchKernelGGL(rf_head_fwd_kernel<false>, dim3(gmr::grid_for(N, 4)), dim3(256), 0, (hipStream_t)stream, N, V, Xt,
+                     X1, ld1, X0, t, (const float*)nullptr, (int64_t)0, 0.f, guidance_scale, pred, row_parts);
+  GMR_LAUNCHED();
+  return GMR_OK;
+}
+
+extern "C" int gmr_rf_head_prior_fwd(int64_t N, float* V, const float* Xt, const float* X1, int64_t ld1,
+                                     const float* X0, const float* t, const float* prior, int64_t ldp,
+                                     float prior_scale, float cos_scale, float* pred, double* row_parts,
+                                     void* stream) {
+  GMR_ARG(N >= 1 && V && Xt && X1 && X0 && t && pred && row_parts && ld1 >= D, "bad args");
+  GMR_ARG(prior && ldp >= D, "prior must be an N x 64 table with a row stride >= 64");
+  hipLaunchKernelGGL(rf_head_fwd_kernel<true>, dim3(gmr::grid_for(N, 4)), dim3(256), 0, (hipStream_t)stream, N, V, Xt,
+                     X1, ld1, X0, t, prior, ldp, prior_scale, cos_scale, pred, row_parts);
   GMR_LAUNCHED();
   return GMR_OK;
 }

@@ -200,7 +200,10 @@ SIGNATURES = {
     "gmr_rf_time_embed": (I32, [I64, P, P, P]),
     "gmr_rf_interp": (I32, [I64, P, I64, P, P, P, P]),
     "gmr_rf_head_fwd": (I32, [I64, P, P, P, I64, P, P, F32, P, P, P]),
+    "gmr_rf_head_prior_fwd": (I32, [I64, P, P, P, I64, P, P, P, I64, F32, F32, P, P, P]),
     "gmr_rf_head_bwd": (I32, [I64, P, P, I64, P, P, P, P, P]),
+    "gmr_rf_item_inputs_ws_floats": (I64, [I64]),
+    "gmr_rf_item_inputs": (I32, [I64, I64, P, I64, P, I64, P, I64, P, I64, P, P]),
     "gmr_rf_losses": (I32, [I64, P, I64, P, F32, P, P]),
     "gmr_rf_infonce_sampled_fwd_bwd": (I32, [I32, I64, P, I64, P, I64, I64, P, I32, P, U64, U64, U64, F32, F32, P, P,
                                              I64, P]),

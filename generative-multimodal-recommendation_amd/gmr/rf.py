@@ -5,7 +5,8 @@ condition table ((U + I) x C) and mixes generate()'s output into its evaluation 
 Supported: embedding_dim 64, rf_hidden_dim 128, rf_n_layers 1..4, C in {64, 128}, 1-RF (use_2rf False).
 
   train_step   X0 ~ N(0, 1), t ~ U[0, 1), X_t; the velocity net forward with saved pre-activations (the Linear
-               layers on the GEMM with the BIAS epilogue, gmr_rf_act_fwd rows between them); the guidance / MSE head;
+               layers on the GEMM with the BIAS epilogue, gmr_rf_act_fwd rows between them); the guidance / MSE head
+               (gmr_rf_head_fwd, or gmr_rf_head_prior_fwd when the backbone passes a user_prior table);
                the two sampled InfoNCE terms on the predicted end points; the backward through the same layers (dW =
                dY^T X, db = colsum(dY), dX = dY W; gmr_rf_act_bwd); one AdamW step on the velocity slab
   generate     the Euler integration in one launch (gmr_rf_sample), or composed per layer from the same kernels
@@ -24,6 +25,7 @@ from .slab import Slab
 H, D = 128, 64
 SITE_X0, SITE_T, SITE_NEG_ITEMS, SITE_NEG_USERS, SITE_Z0, SITE_DROP = 0, 1, 2, 3, 4, 16
 GUIDANCE_SCALE = 0.1  # cosine_guidance_scale; cosine_decay_power 2 is in the kernel
+PRIOR_SCALE = 0.2  # user_guidance_scale (guidance_decay_power 2 likewise): the constructor defaults, no backbone sets them
 
 
 def param_specs(C, n_layers):
@@ -226,10 +228,12 @@ class RFGenerator(nn.Module):
                   contrib.stride(0), stream())
 
     def train_step(self, X1, cond, users, pos, X0=None, t=None, neg_items=None, neg_users=None, masks=None,
-                   apply=True):
+                   apply=True, prior=None):
         """compute_loss_and_step (rf_modules.py:779-894).  X1: N x 64 (any row stride), cond: N x C, users / pos:
         int32 batch indices.  Returns the device tensor [rf_loss, cl_loss, total]; the velocity gradients stay in
-        the slab gradient.  X0 / t / neg_* / masks: injected draws; apply=False skips the AdamW step."""
+        the slab gradient.  X0 / t / neg_* / masks: injected draws; apply=False skips the AdamW step.  prior: the
+        backbone's user_prior, N x 64 fp32 of any row stride >= 64 (a constant of the step: v += (1 - t)^2 0.2 prior
+        before the cosine term, rf_modules.py:460-465); None: no such term."""
         N, U, B = self.N, self.U, users.numel()
         w = self._work(B)
         i32 = lambda a: None if a is None else a.to(self.dev).to(torch.int32).contiguous()  # noqa: E731
@@ -245,8 +249,15 @@ class RFGenerator(nn.Module):
         _lib.call("gmr_rf_interp", N, ptr(X1), X1.stride(0), ptr(w["X0"]), ptr(w["t"]), ptr(w["Xt"]), stream())
         _lib.call("gmr_rf_time_embed", N, ptr(w["t"]), ptr(w["S"]), stream())
         V = self._net_fwd(w, w["Xt"], w["S"], cond, masks)
-        _lib.call("gmr_rf_head_fwd", N, ptr(V), ptr(w["Xt"]), ptr(X1), X1.stride(0), ptr(w["X0"]), ptr(w["t"]),
-                  GUIDANCE_SCALE, ptr(w["pred"]), ptr(w["rowparts"]), stream())
+        if prior is None:
+            _lib.call("gmr_rf_head_fwd", N, ptr(V), ptr(w["Xt"]), ptr(X1), X1.stride(0), ptr(w["X0"]), ptr(w["t"]),
+                      GUIDANCE_SCALE, ptr(w["pred"]), ptr(w["rowparts"]), stream())
+        else:
+            if prior.dtype != torch.float32 or tuple(prior.shape) != (N, D) or prior.stride(1) != 1:
+                raise ValueError(f"prior must be a {N} x {D} fp32 table with unit column stride")
+            _lib.call("gmr_rf_head_prior_fwd", N, ptr(V), ptr(w["Xt"]), ptr(X1), X1.stride(0), ptr(w["X0"]),
+                      ptr(w["t"]), ptr(prior), prior.stride(0), PRIOR_SCALE, GUIDANCE_SCALE, ptr(w["pred"]),
+                      ptr(w["rowparts"]), stream())
         # contrib rows [users | positive items] -> one sorted scatter into dpred (anchors repeat)
         coef = self.weight / B
         cp, cb = w["clparts"], w["contrib"]

@@ -808,8 +808,26 @@ int gmr_rf_interp(int64_t N, const float* X1, int64_t ld1, const float* X0, cons
  * Backward: dV = 2 (V - (X1 - X0)) / (64 N) + (1 - t) dpred. */
 int gmr_rf_head_fwd(int64_t N, float* V, const float* Xt, const float* X1, int64_t ld1, const float* X0,
                     const float* t, float guidance_scale, float* pred, double* row_parts, void* stream);
+/* The head with the user-prior guidance term (:457-476, the backbones that pass user_prior): with lam = (1 - t)^2,
+ * V <- (V + lam prior_scale prior) + lam cos_scale cosine_similarity_gradient(X_t, X1), the two terms added in the
+ * reference's order; prior N x 64 with row stride ldp >= 64.  row_parts, pred and the backward (which reads the
+ * updated V; both terms are constants of the parameters) are gmr_rf_head_fwd's.  An all-zero prior gives
+ * gmr_rf_head_fwd's result bit for bit. */
+int gmr_rf_head_prior_fwd(int64_t N, float* V, const float* Xt, const float* X1, int64_t ld1, const float* X0,
+                          const float* t, const float* prior, int64_t ldp, float prior_scale, float cos_scale,
+                          float* pred, double* row_parts, void* stream);
 int gmr_rf_head_bwd(int64_t N, const float* V, const float* X1, int64_t ld1, const float* X0, const float* t,
                     const float* dpred, float* dV, void* stream);
+/* RFBM3's RF inputs (models/rfbm3.py:107-175) from BM3's projected item tables T = text_trs(text), V =
+ * image_trs(image) (I x 64, strides ldt / ldv; either may be NULL): the item rows U .. U + I - 1 of cond ((U + I) x
+ * C, ldc) = [V | T] (C = 128; one table: that block alone, C = 64) and of prior ((U + I) x 64, ldp) = Z - mean over
+ * the items of Z, Z = V + T.  The user rows are never touched (zero in the reference; the caller zeroes them
+ * once).  The column means are block partials added in one fixed order: no float atomics, two runs are
+ * bit-identical.  ws: gmr_rf_item_inputs_ws_floats(I) floats.  All pointers 16-byte aligned, strides multiples of
+ * 4 floats. */
+int64_t gmr_rf_item_inputs_ws_floats(int64_t I);
+int gmr_rf_item_inputs(int64_t I, int64_t U, const float* T, int64_t ldt, const float* V, int64_t ldv, float* cond,
+                       int64_t ldc, float* prior, int64_t ldp, float* ws, void* stream);
 /* out3 = [rf_loss = sum(row_parts) / (64 N), cl_loss = sum(cl_parts[0 : 2B]) / B, rf_loss + weight cl_loss] */
 int gmr_rf_losses(int64_t N, const double* row_parts, int64_t B, const double* cl_parts, float weight, float* out3,
                   void* stream);
