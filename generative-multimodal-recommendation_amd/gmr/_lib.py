@@ -236,6 +236,16 @@ SIGNATURES = {
                                    I64, U64, U64, U64, P, P, P, P, I64, P, P, I64, P, P, P]),
     "gmr_bm3_loss_reduce": (I32, [I32, P, P, I32, I32, F32, F32, F32, I64, P, P]),
     "gmr_bm3_reg_bwd": (I32, [I64, I64, P, P, I64, P, I64, P]),
+    # MGCN
+    "gmr_mgcn_tile_rows": (I32, []),
+    "gmr_mgcn_max_blocks": (I32, []),
+    "gmr_mgcn_purify_fwd": (I32, [I64, P, I64, P, I64, P, I64, P, P, P, P, I64, P, P, I64, P, P, I64, P]),
+    "gmr_mgcn_purify_bwd": (I32, [I64, P, P, I64, P, P, I64, P, I64, P, P, I64, P, I64, I32, P, I64, P, P, I64, P]),
+    "gmr_mgcn_fuse_fwd": (I32, [I64, P, P, I64, P, I64, P, P, P, P, P, P, P, I64, P, P, I64, P, P, P, P, I64, P, P]),
+    "gmr_mgcn_fuse_bwd": (I32, [I64, P, I64, P, P, I64, P, P, I64, P, P, P, P, I64, P, P, P, P, P, I64, P, P, I64, P,
+                                I64, P, P, P, P, I64, P, I64, P]),
+    "gmr_mgcn_bpr_reg_fwd_bwd": (I32, [I32, I64, P, I64, P, P, P, F32, F32, F32, P, P, I64, P]),
+    "gmr_mgcn_loss_reduce": (I32, [I32, P, F32, F32, F32, F32, P, P]),
 }
 
 _lib = None

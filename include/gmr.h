@@ -965,6 +965,58 @@ int gmr_bm3_loss_reduce(int32_t B, const float* terms, const float* sqnorms, int
 int gmr_bm3_reg_bwd(int64_t n_rows, int64_t n_users, const float* coef, const float* G, int64_t ldg, float* dG,
                     int64_t ldd, void* stream);
 
+/* ---------------------------------------------------------------- MGCN (models/mgcn.py; csrc/mgcn.hip)
+ * Row-local fused blocks on the fp32 MFMA: a row's outputs depend on that row's inputs and the weights only, no float
+ * atomics.  Every row array is 64 columns wide with 16-byte aligned rows and its own leading dimension (>= 64,
+ * % 4 == 0); weights are 64 x 64 [out][in] with row stride ldw, biases and w2 64 floats (w2 16-byte aligned).  The
+ * grid is capped at gmr_mgcn_max_blocks() workgroups of gmr_mgcn_tile_rows() rows per trip.
+ *
+ * Purifier (:152-154) over the n item rows, both modalities in one launch:
+ *   gv = sigmoid(V Wgv^T + bgv), gt = sigmoid(T Wgt^T + bgt);  Pv = E * gv, Pt = E * gt
+ * gv, gt (n x 64, ldg) are what the backward reads.  Backward: dE (+)= dPv * gv + dPt * gt (accumulate = 1 adds to
+ * dE); z (n x 128, ldz >= 128) = [zv | zt], zv = dPv * E * gv (1 - gv), the pre-activation rows (dWgv = zv^T V,
+ * dbgv = colsum(zv) on the host side; V and T themselves are not read); dV = zv Wgv, dT = zt Wgt (ld lddv). */
+int32_t gmr_mgcn_tile_rows(void);
+int32_t gmr_mgcn_max_blocks(void);
+int gmr_mgcn_purify_fwd(int64_t n, const float* E, int64_t lde, const float* V, int64_t ldv, const float* T,
+                        int64_t ldt, const float* Wgv, const float* bgv, const float* Wgt, const float* bgt,
+                        int64_t ldw, float* Pv, float* Pt, int64_t ldp, float* gv, float* gt, int64_t ldg,
+                        void* stream);
+int gmr_mgcn_purify_bwd(int64_t n, const float* dPv, const float* dPt, int64_t lddp, const float* gv, const float* gt,
+                        int64_t ldg, const float* E, int64_t lde, const float* Wgv, const float* Wgt, int64_t ldw,
+                        float* dE, int64_t ldde, int32_t accumulate, float* z, int64_t ldz, float* dV, float* dT,
+                        int64_t lddv, void* stream);
+/* Fuser (:187-201) over the n = U + I rows of a, b (ldab) and c (ldc):
+ *   ha = tanh(W1 a + b1), hb = tanh(W1 b + b1);  (wa, wb) = softmax(w2 . ha, w2 . hb);  m = wa a + wb b
+ *   gi = sigmoid(Wi c + bi), gt = sigmoid(Wt c + bt);  side = (gi * (a - m) + gt * (b - m) + m) / 3;  all = c + side
+ * side, all (ldo) and the saved rows ha, hb, gi, gt (lds) and wab (n x 2: wa, wb) are written; equal logits give
+ * wa = wb = 0.5 exactly.  Backward from dall (d loss / d all, ldda) and dside, dcin (the direct gradients of side and
+ * c, ldds; either may be NULL = zero): da, db (lddab), dc (lddc), the pre-activation rows z1a, z1b (of W1 a + b1 and
+ * W1 b + b1), zi, zt (of the two gates; ldz) and r = dq_a ha + dq_b hb (ldr).  Host side: dW1 = z1a^T a + z1b^T b,
+ * db1 = colsum(z1a) + colsum(z1b), dWi = zi^T c, dbi = colsum(zi), the same for Wt, dw2 = colsum(r). */
+int gmr_mgcn_fuse_fwd(int64_t n, const float* a, const float* b, int64_t ldab, const float* c, int64_t ldc,
+                      const float* W1, const float* b1, const float* w2, const float* Wi, const float* bi,
+                      const float* Wt, const float* bt, int64_t ldw, float* side, float* all, int64_t ldo, float* ha,
+                      float* hb, float* gi, float* gt, int64_t lds, float* wab, void* stream);
+int gmr_mgcn_fuse_bwd(int64_t n, const float* dall, int64_t ldda, const float* dside, const float* dcin, int64_t ldds,
+                      const float* a, const float* b, int64_t ldab, const float* ha, const float* hb, const float* gi,
+                      const float* gt, int64_t lds, const float* wab, const float* w2, const float* W1,
+                      const float* Wi, const float* Wt, int64_t ldw, float* da, float* db, int64_t lddab, float* dc,
+                      int64_t lddc, float* z1a, float* z1b, float* zi, float* zt, int64_t ldz, float* r, int64_t ldr,
+                      void* stream);
+/* bpr_loss (:210-222) on rows gathered from all ((n_users + I) x 64, lda): terms[b] = -logsigmoid(<u,p> - <u,n>)
+ * (exact, as gmr_bpr_logsigmoid_f32), terms[B + b] = 0.5 (|u|^2 + |p|^2 + |n|^2); contrib (3B x 64, ldc) =
+ * [du; dp; dn] of inv_norm sum(terms[:B]) + reg_weight / reg_div sum(terms[B:]) for gmr_scatter_sorted_f32 through
+ * the plan of keys [users | n_users + pos | n_users + neg]. */
+int gmr_mgcn_bpr_reg_fwd_bwd(int32_t B, int64_t n_users, const float* all, int64_t lda, const int32_t* users,
+                             const int32_t* pos, const int32_t* neg, float inv_norm, float reg_weight, float reg_div,
+                             float* terms, float* contrib, int64_t ldc, void* stream);
+/* loss (5 floats) = [total, bpr, reg, nce_items, nce_users] from terms (4 x B: the two rows above, then the per-row
+ * InfoNCE values of the item and the user term): bpr = inv_norm sum, reg = reg_weight / reg_div sum, nce = inv_norm
+ * sum, total = bpr + reg + cl_loss (nce_items + nce_users).  Fixed-order fp64 sums. */
+int gmr_mgcn_loss_reduce(int32_t B, const float* terms, float inv_norm, float reg_weight, float reg_div, float cl_loss,
+                         float* loss, void* stream);
+
 /* (Round 5's native executor of a captured HIP graph, gmr_graph_exec_*, was removed in round 6: its replayed
  * step ran slower on the GPU than eager issue; the host tape of gmr/tape.py removes the Python issue cost and
  * keeps the eager streams and order.) */
