@@ -828,6 +828,17 @@ int gmr_rf_head_bwd(int64_t N, const float* V, const float* X1, int64_t ld1, con
 int64_t gmr_rf_item_inputs_ws_floats(int64_t I);
 int gmr_rf_item_inputs(int64_t I, int64_t U, const float* T, int64_t ldt, const float* V, int64_t ldv, float* cond,
                        int64_t ldc, float* prior, int64_t ldp, float* ws, void* stream);
+/* RFMGCN's prior (models/rfmgcn.py:156-172) from MGCN's two modal views a, b ((U + I) x 64, strides lda / ldb; in the
+ * model both are column blocks of one 128-wide table): prior[r] = Z[r] - mean_seg(r)(Z), Z = 0.5 (a + b), the mean
+ * over the U user rows for r < U and over the I item rows otherwise.  prior is (U + I) x 64 with stride ldp; nothing
+ * outside that block is written.  The grid is the user blocks followed by the item blocks (128 rows each), so the
+ * item segment starts at row U for every U; the column means are block partials added in one fixed order by one
+ * workgroup per segment: no float atomics, two runs are bit-identical.  1 <= U, I <= 2^31 - 128 (GMR_ERR_ARG
+ * otherwise: the mean over an empty segment is NaN in the reference; _ws_floats returns -1).  ws:
+ * gmr_rf_view_prior_ws_floats(U, I) floats.  All pointers 16-byte aligned, strides multiples of 4 floats. */
+int64_t gmr_rf_view_prior_ws_floats(int64_t U, int64_t I);
+int gmr_rf_view_prior(int64_t U, int64_t I, const float* a, int64_t lda, const float* b, int64_t ldb, float* prior,
+                      int64_t ldp, float* ws, void* stream);
 /* out3 = [rf_loss = sum(row_parts) / (64 N), cl_loss = sum(cl_parts[0 : 2B]) / B, rf_loss + weight cl_loss] */
 int gmr_rf_losses(int64_t N, const double* row_parts, int64_t B, const double* cl_parts, float weight, float* out3,
                   void* stream);
