@@ -30,9 +30,7 @@ constexpr int D = 64, TR = 16, LDX = D + 4, NS = 4;
 constexpr uint64_t SITE_MIX = 0x9E3779B97F4A7C15ull;
 constexpr float COS_EPS = 1e-8f;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+using gmr::ld4, gmr::st4, gmr::dot4;
 __device__ __forceinline__ float row16_sum(float v) {
 #pragma unroll
   for (int m = 8; m >= 1; m >>= 1) v += __shfl_xor(v, m);

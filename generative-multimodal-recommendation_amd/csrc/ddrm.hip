@@ -309,9 +309,7 @@ __global__ __launch_bounds__(256) void ddrm_chain_kernel(ChainArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ row loss
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+using gmr::ld4, gmr::st4, gmr::dot4;
 __device__ __forceinline__ float row16_sum(float v) {
 #pragma unroll
   for (int m = 8; m >= 1; m >>= 1) v += __shfl_xor(v, m);

@@ -13,8 +13,7 @@ namespace {
 constexpr int kRowsPerBlock = 8;  // film_bwd: rows per workgroup = one row of dw/db partials
 constexpr int kMaxQ = 4;          // float4 per lane at H = 1024
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+using gmr::ld4, gmr::st4;
 __device__ __forceinline__ float4 f4_mul(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
 __device__ __forceinline__ float f4_hsum(float4 a) { return (a.x + a.y) + (a.z + a.w); }
 

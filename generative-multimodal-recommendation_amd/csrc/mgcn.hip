@@ -28,13 +28,11 @@ namespace {
 constexpr int D = 64, TR = 16, LDX = D + 4;
 constexpr int MAX_BLOCKS = 256;  // one workgroup per CU; each stages the weights once and loops over tiles
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+using gmr::ld4, gmr::st4, gmr::mul4;
 // one fixed fma chain: two rows with the same values give the same bits wherever the compiler places the call
 __device__ __forceinline__ float dot4(float4 a, float4 b) {
   return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
 }
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
 __device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ float row16_sum(float v) {
 #pragma unroll

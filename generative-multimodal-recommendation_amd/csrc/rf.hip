@@ -383,8 +383,7 @@ __global__ __launch_bounds__(256) void rf_losses_kernel(int64_t N, const double*
 // ------------------------------------------------------------------------------------------------ sampled InfoNCE
 constexpr uint64_t SITE_MIX = 0x9E3779B97F4A7C15ull;
 
-__device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
+using gmr::mul4, gmr::dot4;
 __device__ __forceinline__ float group16_sum(float v) {  // over the 16 lanes of a row group
 #pragma unroll
   for (int m = 8; m >= 1; m >>= 1) v += __shfl_xor(v, m);

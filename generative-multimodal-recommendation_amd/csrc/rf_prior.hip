@@ -1,0 +1,198 @@
+// The centred priors of the rectified-flow step, prior[r] = Z[r] - mean_seg(r)(Z), for the two backbones that pass one:
+//
+//   gmr_rf_item_inputs   RFBM3 (models/rfbm3.py:107-175 of the reference), from BM3's projected item tables T =
+//                        text_trs(text), V = image_trs(image) (I x 64 each, either may be absent): Z = V + T, the mean
+//                        over the I items.  Writes the item rows of the N x 64 prior table and, on the way, the item rows
+//                        of the N x C condition table = [V | T] (one modality: that block alone).  The user rows of both
+//                        tables are zero in the reference (BM3 has no R); they are zeroed once by the caller and never
+//                        touched here.
+//   gmr_rf_view_prior    RFMGCN (models/rfmgcn.py:156-172), from MGCN's two modal views a = [R Hv; Hv], b = [R Ht; Ht]
+//                        (N x 64 each, N = U + I; in the model both are column blocks of the one table ab): Z =
+//                        0.5 (a + b); the mean is over the U user rows for r < U and over the I item rows otherwise.
+//                        MGCN carries both views to the users over R, so the user half has a mean of its own.
+//
+// Three small kernels behind either entry point, each a template over the functor that forms Z for a row: per-block
+// column sums of Z, the sum of a segment's block partials in one fixed order (one workgroup per segment), Z - mean.
+// The grid is ceil(U / 128) blocks of the first segment followed by ceil(I / 128) of the second, so no block holds
+// rows of both and the second segment starts at row U whatever U mod 128 is; gmr_rf_item_inputs has the first segment
+// alone, on tables that start at the item rows.  No float atomics: two runs are bit-identical.  16 lanes hold a
+// 64-column row as one float4 each, so a wave moves four rows per access.
+#include "gmr_common.h"
+
+namespace {
+
+using gmr::ld4, gmr::st4, gmr::aligned16;
+
+constexpr int D = 64;
+constexpr int RB = 128;  // rows per block: 16 row groups of 16 lanes, 8 rows each
+constexpr int64_t MAX_ROWS = ((int64_t)1 << 31) - RB;
+
+// Z = V + T, or the one table present; STORE: the row of the condition table written on the way, since V and T are in
+// registers
+template <bool STORE>
+struct ItemZ {
+  const float* __restrict__ T;
+  int64_t ldt;
+  const float* __restrict__ V;
+  int64_t ldv;
+  float* __restrict__ cond;
+  int64_t ldc;
+  __device__ __forceinline__ float4 operator()(int64_t row, int c) const {
+    float4 z;
+    if (V && T) {
+      const float4 v = ld4(V + row * ldv + c), t = ld4(T + row * ldt + c);
+      if (STORE) {
+        st4(cond + row * ldc + c, v);
+        st4(cond + row * ldc + D + c, t);
+      }
+      z = gmr::f4_add(v, t);
+    } else {
+      z = V ? ld4(V + row * ldv + c) : ld4(T + row * ldt + c);
+      if (STORE) st4(cond + row * ldc + c, z);
+    }
+    return z;
+  }
+};
+
+struct ViewZ {
+  const float* __restrict__ a;
+  int64_t lda;
+  const float* __restrict__ b;
+  int64_t ldb;
+  __device__ __forceinline__ float4 operator()(int64_t row, int c) const {
+    return gmr::f4_scale(0.5f, gmr::f4_add(ld4(a + row * lda + c), ld4(b + row * ldb + c)));
+  }
+};
+
+// rows [lo, hi) of the block and its segment: block k < nbu of the first covers [128 k, min(U, 128 k + 128)), block
+// k - nbu of the second covers [U + 128 (k - nbu), min(N, ...))
+__device__ __forceinline__ int block_rows(int nbu, int64_t U, int64_t N, int64_t& lo, int64_t& hi) {
+  const int k = blockIdx.x;
+  const bool first = k < nbu;
+  lo = first ? (int64_t)k * RB : U + (int64_t)(k - nbu) * RB;
+  const int64_t end = first ? U : N;
+  hi = lo + RB < end ? lo + RB : end;
+  return first ? 0 : 1;
+}
+
+// parts[block][64] = column sums of Z over the block's rows (row group rg adds its rows i = 0..7 in order, the 16
+// groups are added in order)
+template <class Z>
+__global__ __launch_bounds__(256) void rf_prior_sum_kernel(int nbu, int64_t U, int64_t N, Z z,
+                                                           float* __restrict__ parts) {
+  __shared__ float4 red[16][16];
+  const int rg = threadIdx.x >> 4, c = (threadIdx.x & 15) * 4;
+  int64_t lo, hi;
+  block_rows(nbu, U, N, lo, hi);
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int i = 0; i < RB / 16; ++i) {
+    const int64_t row = lo + i * 16 + rg;
+    if (row < hi) acc = gmr::f4_add(acc, z(row, c));
+  }
+  red[rg][threadIdx.x & 15] = acc;
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    float4 s = red[0][threadIdx.x];
+#pragma unroll
+    for (int g = 1; g < 16; ++g) s = gmr::f4_add(s, red[g][threadIdx.x]);
+    st4(parts + (int64_t)blockIdx.x * D + c, s);
+  }
+}
+
+// mean[seg][c] = (sum of the segment's block partials of column c) / rows(seg), one workgroup per segment: thread
+// (part, c) adds the segment's blocks part, part + MP, ... in order, the MP parts are added in order.  MP is the
+// entry point's own and part of its result: 4 for gmr_rf_item_inputs, 16 for gmr_rf_view_prior (sixteen chains of
+// dependent loads instead of four: at 152 user blocks the four-chain form took longer than either row pass)
+template <int MP>
+__global__ __launch_bounds__(MP * D) void rf_prior_mean_kernel(int nbu, int nbi, int64_t U, int64_t I,
+                                                               const float* __restrict__ parts,
+                                                               float* __restrict__ mean) {
+  __shared__ float red[MP][D];
+  const int seg = blockIdx.x, c = threadIdx.x & 63, part = threadIdx.x >> 6;
+  const int nblk = seg ? nbi : nbu;
+  const float* p = parts + (int64_t)(seg ? nbu : 0) * D;
+  float s = 0.f;
+  for (int i = part; i < nblk; i += MP) s += p[(int64_t)i * D + c];
+  red[part][c] = s;
+  __syncthreads();
+  if (part == 0) {
+    float t = red[0][c];
+#pragma unroll
+    for (int k = 1; k < MP; ++k) t += red[k][c];
+    mean[seg * D + c] = t / (float)(seg ? I : U);
+  }
+}
+
+template <class Z>
+__global__ __launch_bounds__(256) void rf_prior_sub_kernel(int nbu, int64_t U, int64_t N, Z z,
+                                                           const float* __restrict__ mean, float* __restrict__ prior,
+                                                           int64_t ldp) {
+  const int rg = threadIdx.x >> 4, c = (threadIdx.x & 15) * 4;
+  int64_t lo, hi;
+  const float4 m = ld4(mean + block_rows(nbu, U, N, lo, hi) * D + c);
+#pragma unroll
+  for (int i = 0; i < RB / 16; ++i) {
+    const int64_t row = lo + i * 16 + rg;
+    if (row < hi) {
+      const float4 v = z(row, c);
+      st4(prior + row * ldp + c, make_float4(v.x - m.x, v.y - m.y, v.z - m.z, v.w - m.w));
+    }
+  }
+}
+
+}  // namespace
+
+// ==================================================================================================== C ABI
+extern "C" int64_t gmr_rf_item_inputs_ws_floats(int64_t I) { return ((I + RB - 1) / RB + 1) * D; }
+
+extern "C" int gmr_rf_item_inputs(int64_t I, int64_t U, const float* T, int64_t ldt, const float* V, int64_t ldv,
+                                  float* cond, int64_t ldc, float* prior, int64_t ldp, float* ws, void* stream) {
+  GMR_ARG(I >= 1 && I <= MAX_ROWS && U >= 0, "I >= 1 and U >= 0");
+  GMR_ARG(T || V, "at least one of the projected tables T, V");
+  const int64_t C = T && V ? 2 * D : D;
+  GMR_ARG(cond && prior && ws && ldc >= C && ldp >= D && (!T || ldt >= D) && (!V || ldv >= D),
+          "bad pointers or strides");
+  GMR_ARG(aligned16(T) && aligned16(V) && aligned16(cond) && aligned16(prior) && aligned16(ws) && ldt % 4 == 0 &&
+              ldv % 4 == 0 && ldc % 4 == 0 && ldp % 4 == 0,
+          "rows must be 16-byte aligned");
+  const int nblk = gmr::grid_for(I, RB);
+  float* mean = ws + (int64_t)nblk * D;
+  float* ci = cond + U * ldc;  // the item rows: the I rows are the first segment, the second is empty
+  float* pi = prior + U * ldp;
+  hipLaunchKernelGGL(rf_prior_sum_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, nblk, I, I,
+                     ItemZ<true>{T, ldt, V, ldv, ci, ldc}, ws);
+  GMR_LAUNCHED();
+  hipLaunchKernelGGL(rf_prior_mean_kernel<4>, dim3(1), dim3(4 * D), 0, (hipStream_t)stream, nblk, 0, I, (int64_t)0, ws,
+                     mean);
+  GMR_LAUNCHED();
+  hipLaunchKernelGGL(rf_prior_sub_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, nblk, I, I,
+                     ItemZ<false>{T, ldt, V, ldv, nullptr, 0}, mean, pi, ldp);
+  GMR_LAUNCHED();
+  return GMR_OK;
+}
+
+extern "C" int64_t gmr_rf_view_prior_ws_floats(int64_t U, int64_t I) {
+  if (U < 1 || I < 1 || U > MAX_ROWS || I > MAX_ROWS) return -1;
+  return ((U + RB - 1) / RB + (I + RB - 1) / RB + 2) * D;
+}
+
+extern "C" int gmr_rf_view_prior(int64_t U, int64_t I, const float* a, int64_t lda, const float* b, int64_t ldb,
+                                 float* prior, int64_t ldp, float* ws, void* stream) {
+  GMR_ARG(U >= 1 && I >= 1 && U <= MAX_ROWS && I <= MAX_ROWS, "1 <= U, I <= 2^31 - 128 (a mean over no rows is NaN)");
+  GMR_ARG(a && b && prior && ws && lda >= D && ldb >= D && ldp >= D, "bad pointers or strides");
+  GMR_ARG(aligned16(a) && aligned16(b) && aligned16(prior) && aligned16(ws) && lda % 4 == 0 && ldb % 4 == 0 &&
+              ldp % 4 == 0,
+          "rows must be 16-byte aligned");
+  const int nbu = gmr::grid_for(U, RB), nbi = gmr::grid_for(I, RB);
+  float* mean = ws + (int64_t)(nbu + nbi) * D;  // [users | items]
+  const ViewZ z{a, lda, b, ldb};
+  hipLaunchKernelGGL(rf_prior_sum_kernel, dim3(nbu + nbi), dim3(256), 0, (hipStream_t)stream, nbu, U, U + I, z, ws);
+  GMR_LAUNCHED();
+  hipLaunchKernelGGL(rf_prior_mean_kernel<16>, dim3(2), dim3(16 * D), 0, (hipStream_t)stream, nbu, nbi, U, I, ws, mean);
+  GMR_LAUNCHED();
+  hipLaunchKernelGGL(rf_prior_sub_kernel, dim3(nbu + nbi), dim3(256), 0, (hipStream_t)stream, nbu, U, U + I, z, mean,
+                     prior, ldp);
+  GMR_LAUNCHED();
+  return GMR_OK;
+}

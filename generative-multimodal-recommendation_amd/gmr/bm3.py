@@ -58,7 +58,7 @@ import torch.nn as nn
 from . import _lib
 from . import dist
 from . import kernels as K
-from .abstract_recommender import GeneralRecommender
+from .abstract_recommender import EmbeddingRecommender, config_seed, copy64, r4, sort_plan
 from .freedom import _Linear, _Table
 from .kernels import ptr, stream
 from .slab import Slab
@@ -66,10 +66,6 @@ from .slab import Slab
 D = 64
 MAX_TABLES = 8  # GMR_FRD_MAX_LAYERS of include/gmr.h: the layer mean takes n_layers + 1 tables
 SITE_DROP = 0xB30  # streams u, i, t, v draw at sites SITE_DROP + 0..3
-
-
-def _r4(n):
-    return (n + 3) // 4 * 4
 
 
 def check_config(config):
@@ -93,26 +89,16 @@ def check_config(config):
     return L, p
 
 
-class _BM3Loss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, users, pos, neg, *params):
-        loss = model.rec_step(users, pos, neg)
-        ctx.model = model
-        return loss.clone()
+class BM3(EmbeddingRecommender):
+    LOSS_ROWS = 2  # users, items: no negatives
 
-    @staticmethod
-    def backward(ctx, g):
-        return (None, None, None, None, *[gv * g for gv in ctx.model.grad_views()])
-
-
-class BM3(GeneralRecommender):
     def __init__(self, config, dataloader):
         super().__init__(config, dataloader)
         c = config
         self.n_layers, self.dropout = check_config(c)
         self.embedding_dim = self.feat_embed_dim = D
         self.reg_weight, self.cl_weight = float(c["reg_weight"]), float(c["cl_weight"])
-        self.seed = int((c["seed"][0] if isinstance(c["seed"], (list, tuple)) else c["seed"]) or 0)
+        self.seed = config_seed(c)
         U, I, dev = self.n_users, self.n_items, self.device
         N = self.N = U + I
         # parameters in the reference's RNG order (bm3.py:39-56)
@@ -130,7 +116,7 @@ class BM3(GeneralRecommender):
             Dm = feat.shape[1]
             lins[name] = nn.Linear(Dm, D)
             nn.init.xavier_normal_(lins[name].weight)
-            specs += [(name + "_embedding", (I, Dm), _r4(Dm)), (name + "_W", (D, Dm), _r4(Dm)),
+            specs += [(name + "_embedding", (I, Dm), r4(Dm)), (name + "_W", (D, Dm), r4(Dm)),
                       (name + "_b", (D,), None)]
             self.mods.append((name, feat, blk))
         s = self.slab = Slab(specs, dev)
@@ -181,13 +167,6 @@ class BM3(GeneralRecommender):
             out += [s.gview(name + "_embedding"), s.gview(name + "_W"), s.gview(name + "_b")]
         return out
 
-    def _params(self):
-        out = [self.user_embedding.weight, self.item_id_embedding.weight, self.predictor.weight, self.predictor.bias]
-        for name, _, _ in self.mods:
-            trs = getattr(self, name + "_trs")
-            out += [getattr(self, name + "_embedding").weight, trs.weight, trs.bias]
-        return out
-
     def extra_state(self):
         """The Philox step counter: a resumed run draws the keep masks the uninterrupted one would."""
         return {"counters": {"step": int(self._step)}}
@@ -217,12 +196,6 @@ class BM3(GeneralRecommender):
                   (ctypes.c_int64 * n)(*[t.stride(0) for t in tabs]), ptr(h), h.stride(0), ptr(out), out.stride(0),
                   stream())
 
-    def _copy64(self, src, dst, res=None):
-        """dst = src over N x 64 views of any row stride, + res on the item rows (gmr_frd_mean_fwd with one layer)."""
-        _lib.call("gmr_frd_mean_fwd", src.shape[0], self.n_users if res is not None else src.shape[0], 1,
-                  (ctypes.c_void_p * 1)(src.data_ptr()), (ctypes.c_int64 * 1)(src.stride(0)), ptr(res),
-                  res.stride(0) if res is not None else 0, ptr(dst), dst.stride(0), stream())
-
     def _work(self, B):
         if self._w is None or self._w["B"] < B:
             dev = self.device
@@ -232,14 +205,7 @@ class BM3(GeneralRecommender):
         return self._w
 
     def _plan(self, users, items):
-        B = users.numel()
-        keys = torch.stack([users, items]).contiguous()
-        offs = torch.tensor([0, B], dtype=torch.int64, device=self.device)
-        ka = torch.tensor([0, self.n_users], dtype=torch.int32, device=self.device)
-        n2 = 1 << max(1, (2 * B - 1).bit_length())
-        plan = torch.empty((1, n2), dtype=torch.int64, device=self.device)
-        _lib.call("gmr_sort_batch_keys", 1, ptr(keys), ptr(offs), ptr(ka), 2, B, ptr(plan), n2, n2, stream())
-        return plan[0]
+        return sort_plan((users, items), (0, self.n_users))
 
     def _tables(self):
         has = {name for name, _, _ in self.mods}
@@ -305,31 +271,21 @@ class BM3(GeneralRecommender):
         dg = gtab[:, :D]
         _lib.call("gmr_bm3_reg_bwd", N, U, ptr(self._loss[8:10]), ptr(g), g.stride(0), ptr(dg), dg.stride(0), stream())
         for name, _, blk in self.mods:
-            dT = gtab[U:, D * (1 + blk):D * (2 + blk)]
-            K.gemm(dT, s.view(name + "_embedding"), s.gview(name + "_W"), trans_a=True)   # dW = dT^T raw
-            K.colsum(dT, s.gview(name + "_b"))                                              # db
-            K.gemm(dT, s.view(name + "_W"), s.gview(name + "_embedding"))                   # draw = dT W
+            self._proj_bwd(name, gtab[U:, D * (1 + blk):D * (2 + blk)])
         # dE = (1 / (L + 1)) sum_k adj^k dg: t <- dg; L times t <- adj t + dg, the last one scaled; then the
         # residual: + dg on the item rows
         src = dg
         for i in range(L):
             dst = self._t[i % 2]
-            self._copy64(dg, dst)
+            copy64(dg, dst)
             sc = 1.0 / (L + 1) if i == L - 1 else 1.0
             self.norm_adj.spmm(dst, [(src,)], alpha=sc, beta=sc)
             src = dst
-        self._copy64(src, s.gview("E"), res=dg[U:])
+        copy64(src, s.gview("E"), res=dg[U:])
 
     def loss_terms(self):
         """[total, ui, iu, t, v, tv, vt, reg] of the last rec_step (device tensor)."""
         return self._loss[:8]
-
-    def calculate_loss(self, interaction):
-        users, pos = (interaction[i].to(torch.int32).contiguous() for i in range(2))
-        params = self._params()
-        for p in params:
-            p.grad = None
-        return _BM3Loss.apply(self, users, pos, None, *params)
 
     # ------------------------------------------------------------------ prediction
     @torch.no_grad()
@@ -345,25 +301,3 @@ class BM3(GeneralRecommender):
         self._forward(self._eval)
         K.gemm(self._eval, s.view("Wp"), self._pred, trans_b=True, epi=K.EPI_BIAS, bias=s.view("bp"))
         return self._pred[:self.n_users], self._pred[self.n_users:]
-
-    @torch.no_grad()
-    def topk_from_embeddings(self, usr, itm, users_i32, mask_rows, mask_cols, k, out_idx, scores_buf, out_val=None):
-        E = users_i32.numel()
-        ub = scores_buf.new_empty((E, D))
-        K.gather_rows(usr, users_i32, ub)
-        sc = scores_buf[:E, :self.n_items]
-        K.gemm(ub, itm, sc, trans_b=True)
-        K.mask_scores(sc, mask_rows, mask_cols)
-        K.topk_rows(sc, k, out_idx, out_val)
-        return out_idx
-
-    @torch.no_grad()
-    def full_sort_predict(self, interaction):
-        users = interaction[0].to(torch.int32).contiguous()
-        usr, itm = self.forward_embeddings()
-        E = users.numel()
-        ub = torch.empty((E, D), device=self.device)
-        K.gather_rows(usr, users, ub)
-        scores = torch.empty((E, self.n_items), device=self.device)
-        K.gemm(ub, itm, scores, trans_b=True)
-        return scores

@@ -17,6 +17,7 @@ import scipy.sparse as sp
 import torch
 
 from . import _lib
+from .abstract_recommender import config_seed
 from .kernels import ptr, stream
 
 
@@ -49,7 +50,7 @@ class TrainDataLoader:
         self.n_users, self.n_items = dataset.get_user_num(), dataset.get_item_num()
         self.all_items_np = np.unique(self.i_np).astype(np.int32)
         self.uptr_np, self.uitems_np = user_csr(self.n_users, self.u_np, self.i_np)
-        self.seed = int((config["seed"][0] if isinstance(config["seed"], (list, tuple)) else config["seed"]) or 0)
+        self.seed = config_seed(config)
         self._epoch = 0
         self._dev = None
         self.pr = 0

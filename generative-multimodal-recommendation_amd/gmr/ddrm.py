@@ -65,7 +65,7 @@ import torch.nn as nn
 from . import _lib
 from . import dist
 from . import kernels as K
-from .abstract_recommender import GeneralRecommender
+from .abstract_recommender import EmbeddingRecommender, config_seed, copy64, sort_plan
 from .freedom import _Linear, _Table
 from .kernels import ptr, stream
 from .slab import Slab
@@ -175,19 +175,7 @@ class _DNN(nn.Module):
         self.out_layers = nn.ModuleList([outl])
 
 
-class _DDRMLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, users, pos, neg, *params):
-        loss = model.rec_step(users, pos, neg)
-        ctx.model = model
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        return (None, None, None, None, *[gv * g for gv in ctx.model.grad_views()])
-
-
-class DDRM(GeneralRecommender):
+class DDRM(EmbeddingRecommender):
     def __init__(self, config, dataloader):
         super().__init__(config, dataloader)
         c = config
@@ -197,7 +185,7 @@ class DDRM(GeneralRecommender):
         self.reg_weight, self.alpha, self.beta = float(c["reg_weight"]), float(c["alpha"]), float(c["beta"])
         self.sampling_steps = int(c["sampling_steps"] or 0)
         self.sampling_noise = bool(c["sampling_noise"])
-        self.seed = int((c["seed"][0] if isinstance(c["seed"], (list, tuple)) else c["seed"]) or 0)
+        self.seed = config_seed(c)
         U, I, dev = self.n_users, self.n_items, self.device
         N = self.N = U + I
 
@@ -299,10 +287,6 @@ class DDRM(GeneralRecommender):
         _lib.call("gmr_frd_mean_fwd", self.N, self.n_users, n, (ctypes.c_void_p * n)(*[t.data_ptr() for t in tabs]),
                   (ctypes.c_int64 * n)(*[t.stride(0) for t in tabs]), None, 0, ptr(out), out.stride(0), stream())
 
-    def _copy64(self, src, dst):
-        _lib.call("gmr_frd_mean_fwd", src.shape[0], src.shape[0], 1, (ctypes.c_void_p * 1)(src.data_ptr()),
-                  (ctypes.c_int64 * 1)(src.stride(0)), None, 0, ptr(dst), dst.stride(0), stream())
-
     def _time_table(self, m):
         """E = emb_layer(temb(0..T-1)) (T x 64) and TB = E W1[:, 64:128]^T + b1 (T x H) of denoiser m."""
         s = self.slab
@@ -325,14 +309,7 @@ class DDRM(GeneralRecommender):
         return self._w
 
     def _plan(self, users, pos, neg):
-        B = users.numel()
-        keys = torch.stack([users, pos, neg]).contiguous()
-        offs = torch.tensor([0, B], dtype=torch.int64, device=self.device)
-        ka = torch.tensor([0, self.n_users, self.n_users], dtype=torch.int32, device=self.device)
-        n2 = 1 << max(1, (3 * B - 1).bit_length())
-        plan = torch.empty((1, n2), dtype=torch.int64, device=self.device)
-        _lib.call("gmr_sort_batch_keys", 1, ptr(keys), ptr(offs), ptr(ka), 3, B, ptr(plan), n2, n2, stream())
-        return plan[0]
+        return sort_plan((users, pos, neg), (0, self.n_users, self.n_users))
 
     # ------------------------------------------------------------------ training
     def denoise_fwd(self, m, X, idx_x, C, idx_c, t, TB, out, noise=None, keep=None, drop=None, xd=None, keep_out=None,
@@ -430,13 +407,13 @@ class DDRM(GeneralRecommender):
         K.zero_(gtab)
         _lib.call("gmr_scatter_sorted_f32", plan_bpr.numel(), D, ptr(plan_bpr), ptr(contrib), D, ptr(gtab), D, stream())
         # dE = (1 / (L + 1)) sum_k adj^k g as a Horner chain (adj is symmetric)
-        self._copy64(gtab, gE)
+        copy64(gtab, gE)
         src = gtab
         for i in range(L):
             last = i == L - 1
             dst = gE if last else self._t[i % 2]
             if not last:
-                self._copy64(gtab, dst)
+                copy64(gtab, dst)
             sc = 1.0 / (L + 1) if last else 1.0
             adj.spmm(dst, [(src,)], alpha=sc, beta=sc)
             src = dst
@@ -450,16 +427,6 @@ class DDRM(GeneralRecommender):
     def loss_terms(self):
         """[w | softplus | recon | loss_b] (4 x B) of the last rec_step (device tensor)."""
         return self._terms
-
-    def _params(self):
-        return [p for _, p in self.named_parameters()]
-
-    def calculate_loss(self, interaction):
-        users, pos, neg = (interaction[i].to(torch.int32).contiguous() for i in range(3))
-        params = self._params()
-        for p in params:
-            p.grad = None
-        return _DDRMLoss.apply(self, users, pos, neg, *params)
 
     # ------------------------------------------------------------------ prediction
     @torch.no_grad()
@@ -490,25 +457,3 @@ class DDRM(GeneralRecommender):
         if noise is None or (self.sampling_noise and sn is None):
             self._eval_pass += 1
         return self._gen, ia
-
-    @torch.no_grad()
-    def topk_from_embeddings(self, usr, itm, users_i32, mask_rows, mask_cols, k, out_idx, scores_buf, out_val=None):
-        E = users_i32.numel()
-        ub = scores_buf.new_empty((E, D))
-        K.gather_rows(usr, users_i32, ub)
-        sc = scores_buf[:E, :self.n_items]
-        K.gemm(ub, itm, sc, trans_b=True)
-        K.mask_scores(sc, mask_rows, mask_cols)
-        K.topk_rows(sc, k, out_idx, out_val)
-        return out_idx
-
-    @torch.no_grad()
-    def full_sort_predict(self, interaction, noise=None, step_noise=None):
-        users = interaction[0].to(torch.int32).contiguous()
-        usr, itm = self.forward_embeddings(noise, step_noise)
-        E = users.numel()
-        ub = torch.empty((E, D), device=self.device)
-        K.gather_rows(usr, users, ub)
-        scores = torch.empty((E, self.n_items), device=self.device)
-        K.gemm(ub, itm, scores, trans_b=True)
-        return scores

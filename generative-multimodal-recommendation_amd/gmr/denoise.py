@@ -16,12 +16,9 @@ import torch.nn as nn
 from . import _lib
 from . import dist
 from . import kernels as K
+from .abstract_recommender import r4
 from .kernels import ptr, stream
 from .slab import Slab
-
-
-def _r4(n):
-    return (n + 3) // 4 * 4
 
 
 # GMR_PSAMPLE_FOLD (default 1): p_sample chains (the DiffMM graph rebuild, DiffRec's prediction) carry the
@@ -46,10 +43,10 @@ class Denoiser(nn.Module):
             raise NotImplementedError("Denoise(norm=True) is not on the configured hot path")
         I, H, E = n_items, hidden, emb_size
         self.I, self.H, self.E = I, H, E
-        self.ld_w1 = _r4(I + E)
+        self.ld_w1 = r4(I + E)
         self.keep_prob = 1.0 - dropout
         self.slab = Slab([("emb_W", (E, E), None), ("emb_b", (E,), None), ("W1", (H, I + E), self.ld_w1),
-                          ("b1", (H,), None), ("W2", (I, H), _r4(H)), ("b2", (I,), None)], device)
+                          ("b1", (H,), None), ("W2", (I, H), r4(H)), ("b2", (I,), None)], device)
         self.emb_layer = _Linear(self.slab.parameter("emb_W"), self.slab.parameter("emb_b"))
         self.in_layers = nn.ModuleList([_Linear(self.slab.parameter("W1"), self.slab.parameter("b1"))])
         self.out_layers = nn.ModuleList([_Linear(self.slab.parameter("W2"), self.slab.parameter("b2"))])
@@ -100,7 +97,7 @@ class Denoiser(nn.Module):
         """W1T = W1[:, :I]^T (I x H), the gather-friendly copy used by hidden_sparse; call after
         the weights change (once per graph rebuild / prediction pass)."""
         if getattr(self, "_w1t", None) is None:
-            self._w1t = torch.empty((self.I, _r4(self.H)), device=self.device)[:, :self.H]
+            self._w1t = torch.empty((self.I, r4(self.H)), device=self.device)[:, :self.H]
         _lib.call("gmr_transpose_f32", self.H, self.I, ptr(self.slab.view("W1")), self.ld_w1, ptr(self._w1t),
                   self._w1t.stride(0), stream())
         if PSAMPLE_FOLD:
@@ -111,8 +108,8 @@ class Denoiser(nn.Module):
         """P = W1[:, :I] @ W2 (H x H) and v = W1[:, :I] @ b2 (H) for p_sample_fold; recomputed with W1T."""
         H = self.H
         if getattr(self, "_fold", None) is None:
-            self._fold = (torch.empty((H, _r4(H)), device=self.device)[:, :H],
-                          torch.empty((1, _r4(H)), device=self.device)[:, :H])
+            self._fold = (torch.empty((H, r4(H)), device=self.device)[:, :H],
+                          torch.empty((1, r4(H)), device=self.device)[:, :H])
         P, v = self._fold
         K.gemm(self.W1x(), self.slab.view("W2"), P)                                  # (H x I) (I x H)
         K.gemm(self.slab.view("b2")[None, :], self.W1x(), v, trans_b=True)          # b2 W1[:, :I]^T

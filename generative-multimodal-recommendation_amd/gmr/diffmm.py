@@ -20,7 +20,7 @@ import torch.nn as nn
 from . import _lib
 from . import dist
 from . import kernels as K
-from .abstract_recommender import GeneralRecommender
+from .abstract_recommender import GeneralRecommender, config_seed
 from . import denoise as dn
 from .denoise import Denoiser
 from .kernels import ptr, stream
@@ -128,7 +128,7 @@ class DiffMM(GeneralRecommender):
         self.rebuild_k = int(c["rebuild_k"])
         self.d_emb_size = int(c["d_emb_size"])
         self.norm = c["norm"]
-        self.seed = int((c["seed"][0] if isinstance(c["seed"], (list, tuple)) else c["seed"]) or 0)
+        self.seed = config_seed(c)
         U, I, d = self.n_users, self.n_items, 64
         self.N = U + I
         DV = self.v_feat.shape[1]

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from . import dist
-from .abstract_recommender import GeneralRecommender
+from .abstract_recommender import GeneralRecommender, config_seed
 from . import denoise as dn
 from .denoise import Denoiser
 from .kernels import ptr, stream
@@ -92,7 +92,7 @@ class DiffRec(GeneralRecommender):
         dims = c["dims"] if isinstance(c["dims"], list) else [c["dims"]]
         if len(dims) != 1:
             raise NotImplementedError("one hidden layer (dims = [300]) is the configured hot path")
-        self.seed = int((c["seed"][0] if isinstance(c["seed"], (list, tuple)) else c["seed"]) or 0)
+        self.seed = config_seed(c)
         dev = self.device
         I = self.n_items
         # GaussianDiffusion consumes no RNG; the DNN is built next (diffrec.py:333-353)

@@ -25,16 +25,12 @@ import torch.nn as nn
 from . import _lib
 from . import dist
 from . import kernels as K
-from .abstract_recommender import GeneralRecommender
+from .abstract_recommender import EmbeddingRecommender, config_seed, copy64, r4, sort_plan
 from .kernels import ptr, stream
 from .slab import Slab
 
 # the similarity GEMM of the kNN construction is chunked over rows above this many floats (~1 GB)
 KNN_SIM_FLOATS = 1 << 28
-
-
-def _r4(n):
-    return (n + 3) // 4 * 4
 
 
 class _Linear(nn.Module):
@@ -50,18 +46,6 @@ class _Table(nn.Module):
         self.weight = weight
 
 
-class _FREEDOMLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, users, pos, neg, *params):
-        loss = model.rec_step(users, pos, neg)
-        ctx.model = model
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        return (None, None, None, None, *[gv * g for gv in ctx.model.grad_views()])
-
-
 def knn_topk(feat, k):
     """Per-row top-k of the cosine similarity (freedom.py:79-82): normalised rows, the MFMA GEMM in row
     chunks, gmr_topk_rows_f32.  Returns the n x k int32 index lists (the row itself is among them)."""
@@ -69,13 +53,13 @@ def knn_topk(feat, k):
     dev = feat.device
     if k > n:
         raise ValueError(f"knn_k = {k} exceeds the {n} items")
-    pad = torch.zeros((n, _r4(d)), dtype=torch.float32, device=dev)  # rows padded to 16 bytes with zeros
+    pad = torch.zeros((n, r4(d)), dtype=torch.float32, device=dev)  # rows padded to 16 bytes with zeros
     pad[:, :d].copy_(feat)
     fn = torch.empty_like(pad)
     K.normalize_rows(pad, fn)
     del pad
     ti = torch.empty((n, k), dtype=torch.int32, device=dev)
-    ldn = _r4(n)
+    ldn = r4(n)
     chunk = max(1, min(n, KNN_SIM_FLOATS // ldn))
     sim = torch.empty((chunk, ldn), dtype=torch.float32, device=dev)
     for lo in range(0, n, chunk):
@@ -117,7 +101,7 @@ def prune_select(w, m, u=None, seed=0, step=0):
     return keep
 
 
-class FREEDOM(GeneralRecommender):
+class FREEDOM(EmbeddingRecommender):
     def __init__(self, config, dataloader):
         super().__init__(config, dataloader)
         d = int(config["embedding_size"])
@@ -134,8 +118,7 @@ class FREEDOM(GeneralRecommender):
         self.mm_image_weight = float(config["mm_image_weight"])
         self.dropout = float(config["dropout"])
         # lambda_coeff, cf_model, degree_ratio, weight_size: read by the reference and never used
-        c = config
-        self.seed = int((c["seed"][0] if isinstance(c["seed"], (list, tuple)) else c["seed"]) or 0)
+        self.seed = config_seed(config)
         U, I, dev = self.n_users, self.n_items, self.device
         self.N = U + I
         # parameters in the reference's RNG order (freedom.py:49-62): both nn.Embedding constructors draw
@@ -151,7 +134,7 @@ class FREEDOM(GeneralRecommender):
                 continue
             D = feat.shape[1]
             lins[name] = nn.Linear(D, d)
-            specs += [(name + "_embedding", (I, D), _r4(D)), (name + "_W", (d, D), _r4(D)), (name + "_b", (d,), None)]
+            specs += [(name + "_embedding", (I, D), r4(D)), (name + "_W", (d, D), r4(D)), (name + "_b", (d,), None)]
             self.mods.append((name, feat, blk))
         self.slab = Slab(specs, dev)
         s = self.slab
@@ -207,13 +190,6 @@ class FREEDOM(GeneralRecommender):
         out = [s.gview("E")[:U], s.gview("E")[U:]]
         for name, _, _ in self.mods:
             out += [s.gview(name + "_embedding"), s.gview(name + "_W"), s.gview(name + "_b")]
-        return out
-
-    def _params(self):
-        out = [self.user_embedding.weight, self.item_id_embedding.weight]
-        for name, _, _ in self.mods:
-            trs = getattr(self, name + "_trs")
-            out += [getattr(self, name + "_embedding").weight, trs.weight, trs.bias]
         return out
 
     def extra_state(self):
@@ -284,11 +260,6 @@ class FREEDOM(GeneralRecommender):
                   (ctypes.c_int64 * n)(*[t.stride(0) for t in tabs]), ptr(h), h.stride(0) if h is not None else 0,
                   ptr(out), out.stride(0), stream())
 
-    def _copy64(self, src, dst):
-        """dst = src over N x 64 views of any row stride (gmr_frd_mean_fwd with one layer)."""
-        _lib.call("gmr_frd_mean_fwd", src.shape[0], src.shape[0], 1, (ctypes.c_void_p * 1)(src.data_ptr()),
-                  (ctypes.c_int64 * 1)(src.stride(0)), None, 0, ptr(dst), dst.stride(0), stream())
-
     def _work(self, B):
         if self._w is None or self._w["B"] < B:
             dev = self.device
@@ -297,14 +268,7 @@ class FREEDOM(GeneralRecommender):
         return self._w
 
     def _plan(self, users, pos, neg):
-        B = users.numel()
-        keys = torch.stack([users, pos, neg]).contiguous()
-        offs = torch.tensor([0, B], dtype=torch.int64, device=self.device)
-        ka = torch.tensor([0, self.n_users, self.n_users], dtype=torch.int32, device=self.device)
-        n2 = 1 << max(1, (3 * B - 1).bit_length())
-        plan = torch.empty((1, n2), dtype=torch.int64, device=self.device)
-        _lib.call("gmr_sort_batch_keys", 1, ptr(keys), ptr(offs), ptr(ka), 3, B, ptr(plan), n2, n2, stream())
-        return plan[0]
+        return sort_plan((users, pos, neg), (0, self.n_users, self.n_users))
 
     def loss_fwd_bwd(self, users, pos, neg, inv_norm, w):
         """The three BPR terms of the batch on the work table and their 3B x 192 contribution rows."""
@@ -346,19 +310,16 @@ class FREEDOM(GeneralRecommender):
         _lib.call("gmr_scatter_sorted_f32", plan_bpr.numel(), 192, ptr(plan_bpr), ptr(w["contrib"]), 192, ptr(gtab),
                   192, stream())
         for name, _, blk in self.mods:
-            dT = gtab[U:, 64 * blk:64 * blk + 64]
-            K.gemm(dT, s.view(name + "_embedding"), s.gview(name + "_W"), trans_a=True)   # dW = dT^T raw
-            K.colsum(dT, s.gview(name + "_b"))                                              # db
-            K.gemm(dT, s.view(name + "_W"), s.gview(name + "_embedding"))                   # draw = dT W
+            self._proj_bwd(name, gtab[U:, 64 * blk:64 * blk + 64])
         # dE = (1 / (L + 1)) sum_k adj^k g: t <- g; L times t <- adj t + g; the last one scaled
         g, gE = gtab[:, :64], s.gview("E")
-        self._copy64(g, gE)
+        copy64(g, gE)
         src = g
         for i in range(L):
             last = i == L - 1
             dst = gE if last else self._t[i % 2]
             if not last:
-                self._copy64(g, dst)
+                copy64(g, dst)
             sc = 1.0 / (L + 1) if last else 1.0
             adj.spmm(dst, [(src,)], alpha=sc, beta=sc)
             src = dst
@@ -375,13 +336,6 @@ class FREEDOM(GeneralRecommender):
         """[total, graph, text, image] of the last rec_step (device tensor)."""
         return self._w["loss"]
 
-    def calculate_loss(self, interaction):
-        users, pos, neg = (interaction[i].to(torch.int32).contiguous() for i in range(3))
-        params = self._params()
-        for p in params:
-            p.grad = None
-        return _FREEDOMLoss.apply(self, users, pos, neg, *params)
-
     # ------------------------------------------------------------------ prediction
     @torch.no_grad()
     def forward(self, adj=None):
@@ -397,25 +351,3 @@ class FREEDOM(GeneralRecommender):
     def forward_embeddings(self):
         """full_sort_predict's tables (freedom.py:212-216): forward on norm_adj, the unpruned graph."""
         return self.forward(self.norm_adj)
-
-    @torch.no_grad()
-    def topk_from_embeddings(self, usr, itm, users_i32, mask_rows, mask_cols, k, out_idx, scores_buf, out_val=None):
-        E = users_i32.numel()
-        ub = scores_buf.new_empty((E, 64))
-        K.gather_rows(usr, users_i32, ub)
-        sc = scores_buf[:E, :self.n_items]
-        K.gemm(ub, itm, sc, trans_b=True)
-        K.mask_scores(sc, mask_rows, mask_cols)
-        K.topk_rows(sc, k, out_idx, out_val)
-        return out_idx
-
-    @torch.no_grad()
-    def full_sort_predict(self, interaction):
-        users = interaction[0].to(torch.int32).contiguous()
-        usr, itm = self.forward_embeddings()
-        E = users.numel()
-        ub = torch.empty((E, 64), device=self.device)
-        K.gather_rows(usr, users, ub)
-        scores = torch.empty((E, self.n_items), device=self.device)
-        K.gemm(ub, itm, scores, trans_b=True)
-        return scores

@@ -25,7 +25,7 @@ import torch.nn as nn
 from . import _lib
 from . import dist
 from . import kernels as K
-from .abstract_recommender import GeneralRecommender
+from .abstract_recommender import GeneralRecommender, config_seed
 from .kernels import ptr, stream
 from .kmeans import kmeans_labels
 from .slab import Slab
@@ -138,7 +138,7 @@ class GenRecV1(GeneralRecommender):
             raise NotImplementedError("GenRecV1's forward uses both the image and the text branch (:266-306)")
         if not self.bayesian_samplinge_schedule:
             raise NotImplementedError("bayesian_samplinge_schedule = True (GenRecV1.yaml) is the configured path")
-        self.seed = int((c["seed"][0] if isinstance(c["seed"], (list, tuple)) else c["seed"]) or 0)
+        self.seed = config_seed(c)
         U, I, d = self.n_users, self.n_items, 64
         self.N = U + I
         self.DV, self.DT = self.v_feat.shape[1], self.t_feat.shape[1]

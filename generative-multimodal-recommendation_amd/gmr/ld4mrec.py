@@ -60,17 +60,13 @@ import torch.nn as nn
 from . import _lib
 from . import dist
 from . import kernels as K
-from .abstract_recommender import GeneralRecommender
+from .abstract_recommender import GeneralRecommender, config_seed, r4
 from .denoise import _Linear
 from .kernels import ptr, stream
 from .slab import Slab
 
 MM_DIM = 64          # mm_project output width = embedding_size of the reference yaml
 DROP_SEED = 0x4C44344D  # xor-ed into the seed for the dropout draws (their key space is (seed, step, counter))
-
-
-def _r4(n):
-    return (n + 3) // 4 * 4
 
 
 def check_config(config, n_users, n_items):
@@ -161,7 +157,7 @@ class LD4MRec(GeneralRecommender):
         self.H, self.L, self.steps, self.svd_k = H, L, T, k
         self.gamma = float(c["smoothing_gamma"])
         self.keep_prob = 1.0 - float(c["dropout"] or 0.0)
-        self.seed = int((c["seed"][0] if isinstance(c["seed"], (list, tuple)) else c["seed"]) or 0)
+        self.seed = config_seed(c)
         dev = self.device
         feats = torch.cat([f for f in (self.v_feat, self.t_feat) if f is not None], dim=1)
         D = self.mm_dim = feats.shape[1]
@@ -170,8 +166,8 @@ class LD4MRec(GeneralRecommender):
         self.user_items = torch.as_tensor(dataloader.uitems_np).to(dev)
 
         # ---- parameters (one slab); RNG consumed as the reference's constructor does
-        specs = [("t_in", (1,), None), ("mm_W", (MM_DIM, D), _r4(D)), ("mm_b", (MM_DIM,), None),
-                 ("Wi", (H, I), _r4(I)), ("bi", (H,), None), ("Wc", (H, C), _r4(C)), ("bc", (H,), None),
+        specs = [("t_in", (1,), None), ("mm_W", (MM_DIM, D), r4(D)), ("mm_b", (MM_DIM,), None),
+                 ("Wi", (H, I), r4(I)), ("bi", (H,), None), ("Wc", (H, C), r4(C)), ("bc", (H,), None),
                  ("Wt", (H, H), None), ("bt", (H,), None)]
         for l in range(L):
             specs += [(f"n1w{l}", (H,), None), (f"n1b{l}", (H,), None), (f"W1_{l}", (H, H), None),
@@ -248,7 +244,7 @@ class LD4MRec(GeneralRecommender):
         table = torch.as_tensor(table, dtype=torch.float32)
         if tuple(table.shape) != (self.n_users, self.svd_k):
             raise ValueError(f"user_svd_emb must be {self.n_users} x {self.svd_k}")
-        pad = torch.zeros((self.n_users, _r4(self.svd_k)), dtype=torch.float32, device=self.device)
+        pad = torch.zeros((self.n_users, r4(self.svd_k)), dtype=torch.float32, device=self.device)
         pad[:, :self.svd_k] = table.to(self.device)
         self._svd_pad = pad  # rows padded to a multiple of 4 floats for the float4 gather
         self.user_svd_emb = pad[:, :self.svd_k]
@@ -293,7 +289,7 @@ class LD4MRec(GeneralRecommender):
         if self._w is not None and self._w["B"] >= B:
             return self._w
         I, H, L, T, dev = self.n_items, self.H, self.L, self.steps, self.device
-        Ip, Cp, Dp = _r4(I), _r4(self.cond_dim), _r4(self.mm_dim)
+        Ip, Cp, Dp = r4(I), r4(self.cond_dim), r4(self.mm_dim)
         f = lambda *s, dt=torch.float32: torch.empty(s, dtype=dt, device=dev)  # noqa: E731
         parts = int(_lib.load().gmr_ld4_film_parts_floats(B, H))
         self._w = {"B": B, "x": f(B, Ip), "pred": f(B, Ip), "cond": torch.zeros((B, Cp), device=dev), "mm": f(B, Dp),
@@ -311,7 +307,7 @@ class LD4MRec(GeneralRecommender):
         cond = w["cond"][:B]
         mm = w["mm"][:B, :self.mm_dim]
         # float4 gathers over the zero-padded tables; the mm_project product then overwrites cond[:, k:]
-        K.gather_rows(self._svd_pad, users, cond[:, :_r4(k)])
+        K.gather_rows(self._svd_pad, users, cond[:, :r4(k)])
         K.gather_rows(self._mm_pad, users, w["mm"][:B])
         K.gemm(mm, s.view("mm_W"), cond[:, k:k + MM_DIM], trans_b=True, epi=K.EPI_BIAS, bias=s.view("mm_b"))
         return cond[:, :self.cond_dim], mm

@@ -62,7 +62,7 @@ import torch.nn as nn
 from . import _lib
 from . import dist
 from . import kernels as K
-from .abstract_recommender import GeneralRecommender
+from .abstract_recommender import EmbeddingRecommender, copy64, r4, sort_plan
 from .freedom import KNN_SIM_FLOATS, _Linear, _Table
 from .kernels import ptr, stream
 from .slab import Slab
@@ -77,10 +77,6 @@ TEMP = 0.2
 NCE_FUSED = os.environ.get("GMR_MGCN_NCE_FUSED", "0") == "1"
 # (slab prefix, module name) of the 64 x 64 linears after the projections, in the constructor's order
 GATES = (("gv", "gate_v"), ("gt", "gate_t"), ("pi", "gate_image_prefer"), ("pt", "gate_text_prefer"))
-
-
-def _r4(n):
-    return (n + 3) // 4 * 4
 
 
 def check_config(config, n_items=None, has=(True, True)):
@@ -114,14 +110,14 @@ def knn_graph(feat, k):
     row chunks of at most KNN_SIM_FLOATS floats, as freedom.knn_topk)."""
     n, d = feat.shape
     dev = feat.device
-    pad = torch.zeros((n, _r4(d)), dtype=torch.float32, device=dev)  # rows padded to 16 bytes with zeros
+    pad = torch.zeros((n, r4(d)), dtype=torch.float32, device=dev)  # rows padded to 16 bytes with zeros
     pad[:, :d].copy_(feat)
     fn = torch.empty_like(pad)
     K.normalize_rows(pad, fn)
     del pad
     ti = torch.empty((n, k), dtype=torch.int32, device=dev)
     tv = torch.empty((n, k), dtype=torch.float32, device=dev)
-    ldn = _r4(n)
+    ldn = r4(n)
     chunk = max(1, min(n, KNN_SIM_FLOATS // ldn))
     sim = torch.empty((chunk, ldn), dtype=torch.float32, device=dev)
     for lo in range(0, n, chunk):
@@ -147,19 +143,7 @@ class _Seq(nn.Module):
             self.add_module(str(i), m)
 
 
-class _MGCNLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, users, pos, neg, *params):
-        loss = model.rec_step(users, pos, neg)
-        ctx.model = model
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        return (None, None, None, None, *[gv * g for gv in ctx.model.grad_views()])
-
-
-class MGCN(GeneralRecommender):
+class MGCN(EmbeddingRecommender):
     def __init__(self, config, dataloader):
         super().__init__(config, dataloader)
         c = config
@@ -180,9 +164,9 @@ class MGCN(GeneralRecommender):
         gates = {p: nn.Linear(D, D) for p, _ in GATES}
         specs = [("E", (N, D), None)]
         for name, feat, _ in self.mods:
-            specs.append((name + "_embedding", (I, feat.shape[1]), _r4(feat.shape[1])))
+            specs.append((name + "_embedding", (I, feat.shape[1]), r4(feat.shape[1])))
         for name, feat, _ in self.mods:
-            specs += [(name + "_W", (D, feat.shape[1]), _r4(feat.shape[1])), (name + "_b", (D,), None)]
+            specs += [(name + "_W", (D, feat.shape[1]), r4(feat.shape[1])), (name + "_b", (D,), None)]
         specs += [("q_W1", (D, D), None), ("q_b1", (D,), None), ("q_w2", (1, D), None)]
         for p, _ in GATES:
             specs += [(p + "_W", (D, D), None), (p + "_b", (D,), None)]
@@ -263,15 +247,7 @@ class MGCN(GeneralRecommender):
         s, U = self.slab, self.n_users
         return [s.gview("E")[:U], s.gview("E")[U:]] + [s.gview(n) for n in self._names()]
 
-    def _params(self):
-        return list(self.parameters())
-
     # ------------------------------------------------------------------ forward
-    def _copy64(self, src, dst):
-        """dst = src over n x 64 views of any row stride (gmr_frd_mean_fwd with one layer)."""
-        _lib.call("gmr_frd_mean_fwd", src.shape[0], src.shape[0], 1, (ctypes.c_void_p * 1)(src.data_ptr()),
-                  (ctypes.c_int64 * 1)(src.stride(0)), None, 0, ptr(dst), dst.stride(0), stream())
-
     def _chain(self, graphs, src, dst):
         """dst[:, blk] = graph_m^n src[:, blk] per modality over I x 128 tables (n = n_layers; n = 0 copies)."""
         for name, _, blk in self.mods:
@@ -282,7 +258,7 @@ class MGCN(GeneralRecommender):
                 graphs[name].spmm(y, [(x,)])
                 x = y
             if self.n_layers == 0:
-                self._copy64(x, dst[:, D * blk:D * blk + D])
+                copy64(x, dst[:, D * blk:D * blk + D])
 
     def _forward(self):
         """mgcn.py:146-201 into self.side / self.all (and the rows the backward reads)."""
@@ -320,18 +296,8 @@ class MGCN(GeneralRecommender):
         return self._w
 
     def _plans(self, users, pos, neg):
-        B, U, dev = users.numel(), self.n_users, self.device
-        out = []
-        for keys, add in (((users, pos, neg), (0, U, U)), ((users, pos), (0, U))):
-            nk = len(keys)
-            kt = torch.stack(keys).contiguous()
-            offs = torch.tensor([0, B], dtype=torch.int64, device=dev)
-            ka = torch.tensor(add, dtype=torch.int32, device=dev)
-            n2 = 1 << max(1, (nk * B - 1).bit_length())
-            plan = torch.empty((1, n2), dtype=torch.int64, device=dev)
-            _lib.call("gmr_sort_batch_keys", 1, ptr(kt), ptr(offs), ptr(ka), nk, B, ptr(plan), n2, n2, stream())
-            out.append(plan[0])
-        return out
+        U = self.n_users
+        return [sort_plan((users, pos, neg), (0, U, U)), sort_plan((users, pos), (0, U))]
 
     # ------------------------------------------------------------------ the step
     def rec_step(self, users, pos, neg, plan_bpr=None, plan_cl=None, norm_rows=None, reg_share=1.0):
@@ -372,7 +338,7 @@ class MGCN(GeneralRecommender):
                       stream())
         else:
             if "L" not in w:
-                w["L"] = torch.empty((Bm, _r4(Bm)), dtype=torch.float32, device=self.device)
+                w["L"] = torch.empty((Bm, r4(Bm)), dtype=torch.float32, device=self.device)
             L, g = w["L"][:B, :B], w["g"]
             for k in range(2):
                 v1, v2 = nv[self._i1[k]][:B], nv[self._i2[k]][:B]
@@ -418,13 +384,13 @@ class MGCN(GeneralRecommender):
         self._chain(self.mm_adj_t, dab[U:], self.dpur)
         # dE = (1 / (L + 1)) sum_k adj^k dc: t <- dc; L times t <- adj t + dc, the last one scaled
         gE = s.gview("E")
-        self._copy64(dc, gE)
+        copy64(dc, gE)
         src = dc
         for i in range(L):
             last = i == L - 1
             dst = gE if last else self._t[i % 2]
             if not last:
-                self._copy64(dc, dst)
+                copy64(dc, dst)
             sc = 1.0 / (L + 1) if last else 1.0
             self.norm_adj.spmm(dst, [(src,)], alpha=sc, beta=sc)
             src = dst
@@ -436,20 +402,11 @@ class MGCN(GeneralRecommender):
             z, dv = zp[:, D * blk:D * blk + D], dvt[:, D * blk:D * blk + D]
             K.gemm(z, vt[:, D * blk:D * blk + D], s.gview(p + "_W"), trans_a=True)    # dWg = z^T V
             K.colsum(z, s.gview(p + "_b"))
-            K.gemm(dv, s.view(name + "_embedding"), s.gview(name + "_W"), trans_a=True)   # dW = dV^T raw
-            K.colsum(dv, s.gview(name + "_b"))
-            K.gemm(dv, s.view(name + "_W"), s.gview(name + "_embedding"))               # draw = dV W
+            self._proj_bwd(name, dv)
 
     def loss_terms(self):
         """[total, bpr, reg, nce_items, nce_users] of the last rec_step (device tensor)."""
         return self._loss
-
-    def calculate_loss(self, interaction):
-        users, pos, neg = (interaction[i].to(torch.int32).contiguous() for i in range(3))
-        params = self._params()
-        for p in params:
-            p.grad = None
-        return _MGCNLoss.apply(self, users, pos, neg, *params)
 
     # ------------------------------------------------------------------ prediction
     @torch.no_grad()
@@ -462,25 +419,3 @@ class MGCN(GeneralRecommender):
     def forward_embeddings(self):
         """full_sort_predict's tables (mgcn.py:255-263)."""
         return self.forward()
-
-    @torch.no_grad()
-    def topk_from_embeddings(self, usr, itm, users_i32, mask_rows, mask_cols, k, out_idx, scores_buf, out_val=None):
-        E = users_i32.numel()
-        ub = scores_buf.new_empty((E, D))
-        K.gather_rows(usr, users_i32, ub)
-        sc = scores_buf[:E, :self.n_items]
-        K.gemm(ub, itm, sc, trans_b=True)
-        K.mask_scores(sc, mask_rows, mask_cols)
-        K.topk_rows(sc, k, out_idx, out_val)
-        return out_idx
-
-    @torch.no_grad()
-    def full_sort_predict(self, interaction):
-        users = interaction[0].to(torch.int32).contiguous()
-        usr, itm = self.forward_embeddings()
-        E = users.numel()
-        ub = torch.empty((E, D), device=self.device)
-        K.gather_rows(usr, users, ub)
-        scores = torch.empty((E, self.n_items), device=self.device)
-        K.gemm(ub, itm, scores, trans_b=True)
-        return scores

@@ -13,12 +13,18 @@ Supported: embedding_dim 64, rf_hidden_dim 128, rf_n_layers 1..4, C in {64, 128}
                (fused=False: the comparison path of scripts/rffreedom_step.py)
 
 Random draws come from Philox streams keyed on (seed, step counter, site); each has an injected alternative.
+
+RFBackbone is the mixin of the RF-on-X models (class RFX(RFBackbone, X)): the generator built from the rf_* config
+keys, the warm-up / resume protocol and the "backbone step, then RF step" of rec_step.
 """
+import ctypes
+
 import torch
 import torch.nn as nn
 
 from . import _lib
 from . import kernels as K
+from .abstract_recommender import config_seed, sort_plan
 from .kernels import ptr, stream
 from .slab import Slab
 
@@ -42,16 +48,26 @@ def param_specs(C, n_layers):
     return out
 
 
+# RFGenerator keyword: (config key, default), the constructor defaults of the reference's RF models
+RF_CONFIG = {"n_layers": ("rf_n_layers", 2), "dropout": ("rf_dropout", 0.1), "learning_rate": ("rf_learning_rate", 1e-4),
+             "sampling_steps": ("rf_sampling_steps", 10), "warmup_epochs": ("rf_warmup_epochs", 5),
+             "inference_mix_ratio": ("rf_inference_mix_ratio", 0.2), "contrast_temp": ("rf_contrast_temp", 0.2),
+             "contrast_weight": ("rf_loss_weight", 1.0), "n_negatives": ("rf_infonce_negatives", 1024)}
+
+
+def _get(config, key, default):
+    return config[key] if key in config and config[key] is not None else default
+
+
 def check_config(config):
     """The RF settings this package runs; anything else raises with the key's name."""
-    g = lambda k, d: config[k] if k in config and config[k] is not None else d  # noqa: E731
-    if bool(g("use_denoise", False)):
+    if bool(_get(config, "use_denoise", False)):
         raise NotImplementedError("use_denoise: True needs interaction ratings, which the loaders do not carry")
-    if bool(g("use_2rf", True)):
+    if bool(_get(config, "use_2rf", True)):
         raise NotImplementedError("use_2rf: True (reflow) is not built; set use_2rf: False")
-    if int(g("rf_hidden_dim", 128)) != H:
+    if int(_get(config, "rf_hidden_dim", 128)) != H:
         raise NotImplementedError("rf_hidden_dim must be 128 (the kernels' hidden width)")
-    if not 1 <= int(g("rf_n_layers", 2)) <= 4:
+    if not 1 <= int(_get(config, "rf_n_layers", 2)) <= 4:
         raise NotImplementedError("rf_n_layers must be in 1..4")
 
 
@@ -264,13 +280,9 @@ class RFGenerator(nn.Module):
         self.infonce(w["pred"], X1, 0, U, users, cp[:B], cb[:B], neg_users, SITE_NEG_USERS, coef)
         self.infonce(w["pred"], X1, U, self.I, pos, cp[B:2 * B], cb[B:2 * B], neg_items, SITE_NEG_ITEMS, coef)
         _lib.call("gmr_rf_losses", N, ptr(w["rowparts"]), B, ptr(cp), self.weight, ptr(w["loss"]), stream())
-        keys = torch.stack([users, pos]).contiguous()
-        offs = torch.tensor([0, B], dtype=torch.int64, device=self.dev)
-        n2 = 1 << max(1, (2 * B - 1).bit_length())
-        plan = torch.empty((1, n2), dtype=torch.int64, device=self.dev)
-        _lib.call("gmr_sort_batch_keys", 1, ptr(keys), ptr(offs), ptr(w["ka"]), 2, B, ptr(plan), n2, n2, stream())
+        plan = sort_plan((users, pos), w["ka"])
         K.zero_(w["dpred"])
-        _lib.call("gmr_scatter_sorted_f32", n2, D, ptr(plan), ptr(cb), D, ptr(w["dpred"]), D, stream())
+        _lib.call("gmr_scatter_sorted_f32", plan.numel(), D, ptr(plan), ptr(cb), D, ptr(w["dpred"]), D, stream())
         _lib.call("gmr_rf_head_bwd", N, ptr(V), ptr(X1), X1.stride(0), ptr(w["X0"]), ptr(w["t"]), ptr(w["dpred"]),
                   ptr(w["dV"]), stream())
         self.slab.zero_grad()
@@ -330,3 +342,73 @@ class RFGenerator(nn.Module):
         else:
             out[:] = z
         return out
+
+
+class RFBackbone:
+    """What the RF-on-X models share, mixed in before the backbone: class RFX(RFBackbone, X).  use_rf: False is X and
+    allocates no generator.  The model adds its buffers in __init__ (when use_rf), rf_step_inputs() -> (X1, cond,
+    prior or None), the tables of the last backbone step the RF step trains on, and forward_embeddings(z0=None), its
+    rule for mixing generate()'s rows into the evaluation tables once rf_warm()."""
+
+    def __init__(self, config, dataloader):
+        super().__init__(config, dataloader)
+        self.use_rf = bool(_get(config, "use_rf", True))
+        self.rf_generator = None
+        if not self.use_rf:
+            return
+        check_config(config)
+        self.rf_generator = RFGenerator(self.n_users, self.n_items, 64 * len(self.mods), self.device,
+                                        seed=config_seed(config),
+                                        **{kw: _get(config, key, d) for kw, (key, d) in RF_CONFIG.items()})
+        self._training_epoch = -1  # incremented to 0 by the first pre_epoch_processing
+
+    # ------------------------------------------------------------------ state
+    def extra_state(self):
+        """The backbone's state (none: {}) and the RF counters: a resumed run warms up and draws as the uninterrupted
+        one would."""
+        st = getattr(super(), "extra_state", dict)()
+        if self.use_rf:
+            st.update({"rf_epoch": int(self._training_epoch), "rf_step": int(self.rf_generator.step_ctr)})
+        return st
+
+    def load_extra_state(self, st):
+        getattr(super(), "load_extra_state", lambda st: None)(st)
+        if self.use_rf:
+            self._training_epoch = int(st["rf_epoch"])
+            self.rf_generator.step_ctr = int(st["rf_step"])
+            self.rf_generator.set_epoch(self._training_epoch)
+
+    def pre_epoch_processing(self):
+        super().pre_epoch_processing()
+        if self.use_rf:
+            self._training_epoch += 1
+            self.rf_generator.set_epoch(self._training_epoch)
+
+    def rf_warm(self):
+        return self.use_rf and self.rf_generator.warmed_up()
+
+    # ------------------------------------------------------------------ training
+    def rf_layer_mean(self, n_layers):
+        """X1 of a LightGCN backbone: mean(E_0..E_n) of the last _forward, without the backbone's item term
+        (all_embeddings_ori), into _x1."""
+        tabs = [self.slab.view("E")] + self._layers[:n_layers]
+        n = len(tabs)
+        _lib.call("gmr_frd_mean_fwd", self.N, self.n_users, n, (ctypes.c_void_p * n)(*[t.data_ptr() for t in tabs]),
+                  (ctypes.c_int64 * n)(*[t.stride(0) for t in tabs]), None, 0, ptr(self._x1), self._x1.stride(0),
+                  stream())
+        return self._x1
+
+    def rec_step(self, users, pos, neg, plan_bpr=None, plan_cl=None, norm_rows=None, reg_share=1.0, rf_draws=None,
+                 **backbone_kw):
+        """The backbone's step (backbone_kw: its own injected draws), then the RF step on the tables of that step.  The
+        reference detaches them all, so nothing flows back and the backbone's gradients are the backbone's.  rf_draws:
+        injected draws for RFGenerator.train_step.  rf_loss_terms() reads the RF losses."""
+        loss = super().rec_step(users, pos, neg, plan_bpr, plan_cl, norm_rows, reg_share, **backbone_kw)
+        if self.use_rf:
+            X1, cond, prior = self.rf_step_inputs()
+            self.rf_generator.train_step(X1, cond, users, pos, prior=prior, **(rf_draws or {}))
+        return loss
+
+    def rf_loss_terms(self):
+        """[rf_loss, cl_loss, total] of the last RF step (device tensor)."""
+        return self.rf_generator._w["loss"]

@@ -17,13 +17,9 @@ import torch.nn as nn
 from . import _lib
 from . import dist
 from . import kernels as K
-from .abstract_recommender import GeneralRecommender
+from .abstract_recommender import EmbeddingRecommender, r4, sort_plan
 from .kernels import ptr, stream
 from .slab import Slab
-
-
-def _r4(n):
-    return (n + 3) // 4 * 4
 
 
 class _Linear(nn.Module):
@@ -33,19 +29,7 @@ class _Linear(nn.Module):
         self.bias = bias
 
 
-class _VBPRLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, users, pos, neg, *params):
-        loss = model.rec_step(users, pos, neg)
-        ctx.model = model
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        return (None, None, None, None, *[gv * g for gv in ctx.model.grad_views()])
-
-
-class VBPR(GeneralRecommender):
+class VBPR(EmbeddingRecommender):
     def __init__(self, config, dataloader):
         super().__init__(config, dataloader)
         d = int(config["embedding_size"])
@@ -59,7 +43,7 @@ class VBPR(GeneralRecommender):
         feats = [f for f in (self.t_feat, self.v_feat) if f is not None]
         Kr = sum(f.shape[1] for f in feats)
         self.raw_dim = Kr
-        raw = torch.zeros((I, _r4(Kr)), device=dev)
+        raw = torch.zeros((I, r4(Kr)), device=dev)
         c = 0
         for f in feats:
             raw[:, c:c + f.shape[1]].copy_(f)
@@ -71,7 +55,7 @@ class VBPR(GeneralRecommender):
         lin = nn.Linear(Kr, d)
         nn.init.xavier_normal_(lin.weight.data)
         nn.init.constant_(lin.bias.data, 0)
-        self.slab = Slab([("UI", (U + I, 2 * d), None), ("W", (d, Kr), _r4(Kr)), ("b", (d,), None)], dev)
+        self.slab = Slab([("UI", (U + I, 2 * d), None), ("W", (d, Kr), r4(Kr)), ("b", (d,), None)], dev)
         ui, gui = self.slab.view("UI"), self.slab.gview("UI")
         ui[:U].copy_(g_u)
         ui[U:, :d].copy_(g_i)
@@ -108,14 +92,7 @@ class VBPR(GeneralRecommender):
         return F
 
     def _plan(self, users, pos, neg):
-        B = users.numel()
-        keys = torch.stack([users, pos, neg]).contiguous()
-        offs = torch.tensor([0, B], dtype=torch.int64, device=self.device)
-        ka = torch.tensor([0, self.n_users, self.n_users], dtype=torch.int32, device=self.device)
-        n2 = 1 << max(1, (3 * B - 1).bit_length())
-        plan = torch.empty((1, n2), dtype=torch.int64, device=self.device)
-        _lib.call("gmr_sort_batch_keys", 1, ptr(keys), ptr(offs), ptr(ka), 3, B, ptr(plan), n2, n2, stream())
-        return plan[0]
+        return sort_plan((users, pos, neg), (0, self.n_users, self.n_users))
 
     def rec_step(self, users, pos, neg, plan_bpr=None, plan_cl=None, norm_rows=None, reg_share=1.0):
         """calculate_loss (vbpr.py:76-97) and all parameter gradients (into the slab gradient)."""
@@ -144,38 +121,9 @@ class VBPR(GeneralRecommender):
         _lib.call("gmr_fill2d_f32", dF.shape[0], dF.shape[1], ptr(dF), dF.stride(0), 0.0, stream())
         return w["loss"][0]
 
-    def calculate_loss(self, interaction):
-        users, pos, neg = (interaction[i].to(torch.int32).contiguous() for i in range(3))
-        params = [self.u_embedding, self.i_embedding, self.item_linear.weight, self.item_linear.bias]
-        for p in params:
-            p.grad = None
-        return _VBPRLoss.apply(self, users, pos, neg, *params)
-
     # ------------------------------------------------------------------ prediction
     @torch.no_grad()
     def forward_embeddings(self):
         self._item_features()
         ui = self.slab.view("UI")
         return ui[:self.n_users], ui[self.n_users:]
-
-    @torch.no_grad()
-    def topk_from_embeddings(self, usr, itm, users_i32, mask_rows, mask_cols, k, out_idx, scores_buf, out_val=None):
-        E = users_i32.numel()
-        ub = scores_buf.new_empty((E, self.D))
-        K.gather_rows(usr, users_i32, ub)
-        sc = scores_buf[:E, :self.n_items]
-        K.gemm(ub, itm, sc, trans_b=True)
-        K.mask_scores(sc, mask_rows, mask_cols)
-        K.topk_rows(sc, k, out_idx, out_val)
-        return out_idx
-
-    @torch.no_grad()
-    def full_sort_predict(self, interaction):
-        users = interaction[0].to(torch.int32).contiguous()
-        usr, itm = self.forward_embeddings()
-        E = users.numel()
-        ub = torch.empty((E, self.D), device=self.device)
-        K.gather_rows(usr, users, ub)
-        scores = torch.empty((E, self.n_items), device=self.device)
-        K.gemm(ub, itm, scores, trans_b=True)
-        return scores

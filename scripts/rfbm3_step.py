@@ -89,8 +89,7 @@ res = {"shape": a.shape, "B": B, "U": m.n_users, "I": m.n_items, "N": N, "rf_n_l
 loss = float(m.rec_step(users, pos, neg, plan_cl=plan))
 res["loss_first_step"] = round(loss, 6)
 res["rf_losses_first_step"] = [round(float(x), 6) for x in m.rf_loss_terms().cpu()]
-X1 = m.rf_target()
-cond, prior = m.rf_inputs()
+X1, cond, prior = m.rf_step_inputs()
 w = g._work(B)
 
 
@@ -100,9 +99,10 @@ def step(use_rf):
     m.use_rf = True
 
 
-def inputs():
-    m.rf_target()
-    m.rf_inputs()
+def inputs_alone():
+    T, V = m._tables()
+    _lib.call("gmr_rf_item_inputs", m.n_items, m.n_users, ptr(T), m.tv.stride(0), ptr(V), m.tv.stride(0), ptr(cond),
+              cond.stride(0), ptr(prior), prior.stride(0), ptr(m._inws), stream())
 
 
 def head(with_prior):
@@ -124,8 +124,8 @@ for rnd in range(2):
     res[f"rfbm3_rec_step_ms_{rnd}"] = events(lambda: step(True))
     res[f"rf_train_step_ms_{rnd}"] = events(lambda: g.train_step(X1, cond, users, pos, prior=prior))
     res[f"rf_train_step_no_prior_ms_{rnd}"] = events(lambda: g.train_step(X1, cond, users, pos))
-    res[f"target_inputs_ms_{rnd}"] = events(inputs)
-    res[f"inputs_alone_ms_{rnd}"] = events(m.rf_inputs)
+    res[f"target_inputs_ms_{rnd}"] = events(m.rf_step_inputs)
+    res[f"inputs_alone_ms_{rnd}"] = events(inputs_alone)
     w["V"].zero_()  # the head adds into V: keep it finite over the repetitions
     res[f"head_prior_ms_{rnd}"] = events(lambda: (w["V"].zero_(), head(True)))
     res[f"head_plain_ms_{rnd}"] = events(lambda: (w["V"].zero_(), head(False)))

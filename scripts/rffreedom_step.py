@@ -77,7 +77,7 @@ res["rec_step_freedom_ms"] = events(lambda: m.rec_step(users, pos, neg, plan))
 m.use_rf = True
 
 # ---- the RF training step by phase, on the tables of the last step
-X1, cond = m.rf_target(), m.rf_conditions()
+X1, cond, _ = m.rf_step_inputs()
 w = g._work(B)
 res["rf_train_step_ms"] = events(lambda: g.train_step(X1, cond, users, pos))
 

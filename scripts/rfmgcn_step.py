@@ -107,7 +107,7 @@ res = {"shape": a.shape, "B": B, "U": m.n_users, "I": m.n_items, "N": N, "rf_n_l
 loss = float(m.rec_step(users, pos, neg, pb, pc))
 res["loss_first_step"] = round(loss, 6)
 res["rf_losses_first_step"] = [round(float(x), 6) for x in m.rf_loss_terms().cpu()]
-prior = m.rf_prior()
+prior = m.rf_step_inputs()[2]
 
 
 def step(use_rf):
@@ -120,7 +120,7 @@ for rnd in range(2):
     res[f"mgcn_rec_step_ms_{rnd}"] = events(lambda: step(False))
     res[f"rfmgcn_rec_step_ms_{rnd}"] = events(lambda: step(True))
     res[f"rf_train_step_ms_{rnd}"] = events(lambda: g.train_step(m.all, m.ab, users, pos, prior=prior))
-    res[f"prior_ms_{rnd}"] = events(m.rf_prior)
+    res[f"prior_ms_{rnd}"] = events(m.rf_step_inputs)
     set_warm(False)
     res[f"eval_tables_cold_ms_{rnd}"] = events(m.forward_embeddings)
     set_warm(True)

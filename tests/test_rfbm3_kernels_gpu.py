@@ -150,7 +150,7 @@ def _inputs_run(I, U, tv, hasT, hasV, fill):
     return cond.cpu().numpy(), prior.cpu().numpy()
 
 
-@pytest.mark.parametrize("I", [1, 5, 41, 1100])
+@pytest.mark.parametrize("I", [1, 5, 41, 128, 129, 1100])  # 128 / 129: one full 128-row block, and one row past it
 @pytest.mark.parametrize("U", [0, 3])
 @pytest.mark.parametrize("mods", ["both", "image", "text"])
 def test_item_inputs(I, U, mods):

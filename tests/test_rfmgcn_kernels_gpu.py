@@ -24,7 +24,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 D = 64
 SENT = 7.25
-SHAPES = [(1, 1), (5, 3), (37, 41), (128, 128), (129, 127), (300, 1100)]
+# (2049, 1): 17 user blocks, one more than the sixteen chains of the mean kernel, beside a one-row item segment
+SHAPES = [(1, 1), (5, 3), (37, 41), (128, 128), (129, 127), (300, 1100), (2049, 1)]
 LAYOUTS = ["model", "wide", "contiguous"]
 
 
@@ -120,8 +121,8 @@ def test_view_prior_segments_do_not_mix(U, I):
     # error in that column is one draw of the same size and may be any fraction of the kernel's (seen on the MI355X at
     # (37, 41): 2.0e-5 against 2.1e-5 over the table, yet a column at 2.0e-5 against 0.65e-5).  The bound is the
     # worst case of the kernel's own order instead: an entry passes 7 additions in its row group, 15 over the groups,
-    # 1 + 15 over the sixteen chains of block partials (up to 9 blocks: one block per chain), then the rounding of
-    # a + b, of the division and of the subtraction: 41 <= 48 half-ulps at the magnitude of Z.  It is 3e-4 here; one
+    # 2 + 15 over the sixteen chains of block partials (up to 17 blocks: at most two per chain), then the rounding of
+    # a + b, of the division and of the subtraction: 42 <= 48 half-ulps at the magnitude of Z.  It is 3e-4 here; one
     # foreign row would move a mean by 200 / rows >= 0.18.
     r64, _ = _refs(a, b, U)
     zmax = float(np.abs(0.5 * (a.astype(np.float64) + b)).max())
