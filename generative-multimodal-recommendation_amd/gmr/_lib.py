@@ -248,6 +248,14 @@ SIGNATURES = {
                                 I64, P, P, P, P, I64, P, I64, P]),
     "gmr_mgcn_bpr_reg_fwd_bwd": (I32, [I32, I64, P, I64, P, P, P, F32, F32, F32, P, P, I64, P]),
     "gmr_mgcn_loss_reduce": (I32, [I32, P, F32, F32, F32, F32, P, P]),
+    # LATTICE
+    "gmr_lat_edge_fwd": (I32, [I64, I32, I32, P, I64, P, I64, P, I64, P, I64, P, P, P, I64, P, P, P]),
+    "gmr_lat_adj_fwd": (I32, [I64, I32, I32, P, P, P, I64, P, P, F32, P, P]),
+    "gmr_lat_sddmm": (I32, [I64, I32, P, I64, P, I64, P, I64, I32, P, P]),
+    "gmr_lat_bwd_ds": (I32, [I64, I32, I32, P, P, P, P, P, I64, P, P, P, F32, P, P]),
+    "gmr_lat_bwd_da": (I32, [I64, I32, I32, P, P, P, P, P, I64, P, P, F32, P, P, P]),
+    "gmr_lat_dw_reduce": (I32, [I64, P, P, P, P]),
+    "gmr_lat_bwd_dn": (I32, [I64, I32, I32, P, P, I64, P, I64, P, I64, P, P, P, I64, P, I64, P]),
 }
 
 _lib = None

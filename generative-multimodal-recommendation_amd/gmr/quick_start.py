@@ -63,7 +63,9 @@ def quick_start(model, dataset, config_dict, save_model=True, mg=False):
     hyper = list(config["hyper_parameters"])
     if "seed" not in hyper:
         hyper = ["seed"] + hyper
-    combos = list(product(*[config[i] or [None] for i in hyper]))
+    # a hyper-parameter that holds a scalar is a grid of one value
+    grid = [config[i] if isinstance(config[i], (list, tuple)) else [config[i]] for i in hyper]
+    combos = list(product(*[g or [None] for g in grid]))
     val_metric = config["valid_metric"].lower()
     results, best_idx, best_val = [], 0, 0.0
     for idx, tup in enumerate(combos):

@@ -33,6 +33,8 @@ class Slab:
             self.layout[name] = (tuple(shape), ld)
             off += (size + ALIGN - 1) // ALIGN * ALIGN
         self.numel = max(off, ALIGN)
+        # False while the model leaves this slab without a gradient (torch's .grad = None): FlatAdam.step skips it
+        self.has_grad = True
         self.data = torch.zeros(self.numel, dtype=torch.float32, device=device)
         self.grad = torch.zeros(self.numel, dtype=torch.float32, device=device)
 
@@ -91,6 +93,9 @@ class FlatAdam:
 
     def step(self):
         for s, st in zip(self.slabs, self.state):
+            if not getattr(s, "has_grad", True):
+                # torch.optim.Adam skips a parameter whose .grad is None: no decay of the moments, no step count
+                continue
             st["step"] += 1
             K.adam(s.data, s.grad, st["exp_avg"], st["exp_avg_sq"], self.lr, self.betas[0], self.betas[1], self.eps,
                    self.weight_decay, st["step"])

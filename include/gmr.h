@@ -1028,6 +1028,44 @@ int gmr_mgcn_bpr_reg_fwd_bwd(int32_t B, int64_t n_users, const float* all, int64
 int gmr_mgcn_loss_reduce(int32_t B, const float* terms, float inv_norm, float reg_weight, float reg_div, float cl_loss,
                          float* loss, void* stream);
 
+/* ---------------------------------------------------------------- LATTICE (models/lattice.py): the learned item graph
+ * n items, M <= 2 modalities, k <= 64 neighbours; n_m: the row-normalised projected features (n x 64, ldn), idx_m
+ * (n x k, ldi): each row's top-k of n_m n_m^T.  Edge (i, m, slot) is position q = m k + slot of row i in the n x (M k)
+ * edge arrays (v, dv, oval) and in the first M k of the R = 2 M k columns of item_adj's rows (col: ldc, val: n x R
+ * dense).  mw: the two modal_weight floats on the device, w = softmax(mw) (equal entries: exactly 0.5; M = 1: w = 1,
+ * mw may be NULL).  A column may occur in several slots of a row; all sums are linear in the slots.
+ * edge_fwd:  v = <n_i, n_j> (fixed fma chain + butterfly), col[:, :M k] = idx, r_i = sum_q w_m v, s = r^-1/2
+ *            (0 where r = 0).
+ * adj_fwd:   val[i, q] = (1 - lambda) s_i w_m v s_col for q < M k, lambda w_m oval[i, q - M k] after (oval: the frozen
+ *            original lists' normalised values; their columns are col[:, M k:], written once by the caller).
+ * sddmm:     dA[i, q] (+)= <g[i], h[col[i, q]]> over R columns (the graph's gradient on its pattern).
+ * The backward takes the incoming lists of the learned edges: in_edge = the edge ids i M k + q sorted stably by the
+ * key m n + col, in_ptr (M n + 1) the row pointer over the keys.
+ * bwd_ds:    dr_i = -1/2 s_i^3 (sum_q p_(i,q) s_col + sum_{e -> i} p_e s_row(e)), p = (1 - lambda) dA w_m v; 0 where
+ *            r_i = 0.
+ * bwd_da:    dv = w_m ((1 - lambda) dA s_i s_col + dr_i); parts (n x 2) = the row's share of dw_m = sum da v +
+ *            lambda sum oval dA.
+ * dw_reduce: dmw (2) = the softmax backward of the column sums of parts (fixed-order fp64 tree).
+ * bwd_dn:    dn_m[i] = sum_slot dv n_col + sum_{e -> i} dv_e n_row(e)  (n x 64, ldd).
+ * No float atomics; two runs give the same bits. */
+int gmr_lat_edge_fwd(int64_t n, int32_t k, int32_t M, const float* n0, int64_t ldn0, const int32_t* idx0, int64_t ldi0,
+                     const float* n1, int64_t ldn1, const int32_t* idx1, int64_t ldi1, const float* mw, float* v,
+                     int32_t* col, int64_t ldc, float* r, float* s, void* stream);
+int gmr_lat_adj_fwd(int64_t n, int32_t k, int32_t M, const float* v, const float* s, const int32_t* col, int64_t ldc,
+                    const float* oval, const float* mw, float lambda, float* val, void* stream);
+int gmr_lat_sddmm(int64_t n, int32_t R, const int32_t* col, int64_t ldc, const float* g, int64_t ldg, const float* h,
+                  int64_t ldh, int32_t accumulate, float* dA, void* stream);
+int gmr_lat_bwd_ds(int64_t n, int32_t k, int32_t M, const float* dA, const float* v, const float* r, const float* s,
+                   const int32_t* col, int64_t ldc, const int32_t* in_ptr, const int32_t* in_edge, const float* mw,
+                   float lambda, float* dr, void* stream);
+int gmr_lat_bwd_da(int64_t n, int32_t k, int32_t M, const float* dA, const float* v, const float* s, const float* dr,
+                   const int32_t* col, int64_t ldc, const float* oval, const float* mw, float lambda, float* dv,
+                   float* parts, void* stream);
+int gmr_lat_dw_reduce(int64_t n, const float* parts, const float* mw, float* dmw, void* stream);
+int gmr_lat_bwd_dn(int64_t n, int32_t k, int32_t M, const float* dv, const float* n0, int64_t ldn0, const float* n1,
+                   int64_t ldn1, const int32_t* col, int64_t ldc, const int32_t* in_ptr, const int32_t* in_edge,
+                   float* dn0, int64_t ldd0, float* dn1, int64_t ldd1, void* stream);
+
 /* (Round 5's native executor of a captured HIP graph, gmr_graph_exec_*, was removed in round 6: its replayed
  * step ran slower on the GPU than eager issue; the host tape of gmr/tape.py removes the Python issue cost and
  * keeps the eager streams and order.) */
