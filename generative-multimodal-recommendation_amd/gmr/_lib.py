@@ -256,6 +256,19 @@ SIGNATURES = {
     "gmr_lat_bwd_da": (I32, [I64, I32, I32, P, P, P, P, P, I64, P, P, F32, P, P, P]),
     "gmr_lat_dw_reduce": (I32, [I64, P, P, P, P]),
     "gmr_lat_bwd_dn": (I32, [I64, I32, I32, P, P, I64, P, I64, P, I64, P, P, P, I64, P, I64, P]),
+    # SMORE
+    "gmr_smore_tile_rows": (I32, []),
+    "gmr_smore_max_blocks": (I32, []),
+    "gmr_smore_spectrum_ws_floats": (I64, [I64]),
+    "gmr_smore_twiddles": (I32, [P, P, P]),
+    "gmr_smore_spectrum_fwd": (I32, [I64, P, I64, P, I64, P, I64, P, P, P, P, P, P, P, P, P, I64, P, I64, P, I64, P,
+                                     I64, P, I64, P]),
+    "gmr_smore_spectrum_bwd": (I32, [I64, P, I64, P, I64, P, I64, P, I64, P, P, P, P, P, P, I64, P, I64, I32, P, I64,
+                                     P, P, I64, P, I64, P, P, P, P]),
+    "gmr_smore_fuse_fwd": (I32, [I64, P, I64, P, I64, P, P, P, P, P, P, P, P, P, P, P, P, I64, F32, I32, P, I64, U64,
+                                 U64, P, P, I64, P, I64, P]),
+    "gmr_smore_fuse_bwd": (I32, [I64, P, I64, P, P, I64, P, I64, P, I64, F32, P, P, P, P, P, P, P, I64, P, I64, P,
+                                 I64, P, I64, P]),
 }
 
 _lib = None

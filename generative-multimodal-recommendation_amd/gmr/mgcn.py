@@ -350,10 +350,9 @@ class MGCN(EmbeddingRecommender):
         _lib.call("gmr_mgcn_loss_reduce", B, ptr(terms), float(inv_norm), self.reg_weight, float(self.batch_size),
                   self.cl_loss, ptr(self._loss), stream())
 
-    def step_backward(self, plan_bpr, plan_cl, w, B):
-        """All parameter gradients from the outputs of loss_fwd_bwd over B rows."""
-        s, U, I, N, L = self.slab, self.n_users, self.n_items, self.N, self.n_ui_layers
-        s.zero_grad()
+    def scatter_loss_rows(self, plan_bpr, plan_cl, w, B):
+        """The outputs of loss_fwd_bwd scattered into dall (d loss / d all) and gtab = [dside | dc] (SMORE shares
+        it)."""
         dall, gtab, cs = self.dall, self.gtab, w["cs"][:2 * B]
         K.zero_(dall)
         _lib.call("gmr_scatter_sorted_f32", plan_bpr.numel(), D, ptr(plan_bpr), ptr(w["contrib"]), D, ptr(dall), D,
@@ -365,6 +364,28 @@ class MGCN(EmbeddingRecommender):
         K.zero_(gtab)
         _lib.call("gmr_scatter_sorted_f32", plan_cl.numel(), 2 * D, ptr(plan_cl), ptr(cs), 2 * D, ptr(gtab), 2 * D,
                   stream())
+
+    def behaviour_bwd(self, dc):
+        """dE = (1 / (L + 1)) sum_k adj^k dc into the slab's gradient: t <- dc; L times t <- adj t + dc, the last one
+        scaled."""
+        L, gE = self.n_ui_layers, self.slab.gview("E")
+        copy64(dc, gE)
+        src = dc
+        for i in range(L):
+            last = i == L - 1
+            dst = gE if last else self._t[i % 2]
+            if not last:
+                copy64(dc, dst)
+            sc = 1.0 / (L + 1) if last else 1.0
+            self.norm_adj.spmm(dst, [(src,)], alpha=sc, beta=sc)
+            src = dst
+
+    def step_backward(self, plan_bpr, plan_cl, w, B):
+        """All parameter gradients from the outputs of loss_fwd_bwd over B rows."""
+        s, U, I, N = self.slab, self.n_users, self.n_items, self.N
+        s.zero_grad()
+        self.scatter_loss_rows(plan_bpr, plan_cl, w, B)
+        dall, gtab = self.dall, self.gtab
         ab, c, sv, dab, dc, zf, r = self.ab, self.c, self.saved, self.dab, self.dc, self.zf, self.r
         _lib.call("gmr_mgcn_fuse_bwd", N, ptr(dall), D, ptr(gtab), ptr(gtab[:, D:]), 2 * D, ptr(ab), ptr(ab[:, D:]),
                   2 * D, ptr(sv), ptr(sv[:, D:]), ptr(sv[:, 2 * D:]), ptr(sv[:, 3 * D:]), 4 * D, ptr(self.wab),
@@ -382,18 +403,8 @@ class MGCN(EmbeddingRecommender):
         # dH = da_i + R^T da_u (in place on the item rows), dP = (A^T)^n dH
         self.R_t.spmm(dab[U:], [(dab[:U, :D],), (dab[:U, D:],)], beta=1.0)
         self._chain(self.mm_adj_t, dab[U:], self.dpur)
-        # dE = (1 / (L + 1)) sum_k adj^k dc: t <- dc; L times t <- adj t + dc, the last one scaled
+        self.behaviour_bwd(dc)
         gE = s.gview("E")
-        copy64(dc, gE)
-        src = dc
-        for i in range(L):
-            last = i == L - 1
-            dst = gE if last else self._t[i % 2]
-            if not last:
-                copy64(dc, dst)
-            sc = 1.0 / (L + 1) if last else 1.0
-            self.norm_adj.spmm(dst, [(src,)], alpha=sc, beta=sc)
-            src = dst
         dp, g, zp, dvt, vt = self.dpur, self.gates_i, self.zp, self.dvt, self.vt
         _lib.call("gmr_mgcn_purify_bwd", I, ptr(dp), ptr(dp[:, D:]), 2 * D, ptr(g), ptr(g[:, D:]), 2 * D,
                   ptr(s.view("E")[U:]), D, ptr(s.view("gv_W")), ptr(s.view("gt_W")), D, ptr(gE[U:]), D, 1, ptr(zp),

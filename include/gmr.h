@@ -1066,6 +1066,62 @@ int gmr_lat_bwd_dn(int64_t n, int32_t k, int32_t M, const float* dv, const float
                    int64_t ldn1, const int32_t* col, int64_t ldc, const int32_t* in_ptr, const int32_t* in_edge,
                    float* dn0, int64_t ldd0, float* dn1, int64_t ldd1, void* stream);
 
+/* ---------------------------------------------------------------- SMORE (models/smore.py; csrc/smore.hip)
+ * Row-local fused blocks in mgcn.hip's scheme (fp32 MFMA, 16-row tiles, a grid capped at gmr_smore_max_blocks()
+ * workgroups, no float atomics).  Rows are 16-byte aligned with ld % 4 == 0; packed arrays hold 64-column blocks side
+ * by side.  Weights are 64 x 64 [out][in] with row stride ldw, biases 64 floats.  The kernels take 87 - 143 KB of
+ * dynamic LDS: one workgroup per CU.
+ *
+ * A spectrum row lives in the 64-real layout: column j <= 32 is Re X_j, column j >= 33 is Im X_(j - 32) (Im X_0 and
+ * Im X_32 have no column).  The complex filters Wi, Wt, Wf are 33 x 2 floats (re, im); Im W_0 and Im W_32 are never
+ * read and their gradients are written as 0.  gmr_smore_twiddles copies the two 64 x 64 transform matrices (forward
+ * F[j][n], inverse Gt[n][j] = c_j F[j][n], built once per device in double and rounded) for tests.
+ *
+ * spectrum_fwd over the n item rows of V, T (the projected features) and E (the item id rows):
+ *   A = rfft(V), B = rfft(T) (norm 'ortho');  conv = [irfft(A Wi) | irfft(B Wt) | irfft(A B Wf)]  (n x 192, ldcv)
+ *   g = sigmoid(conv_m Wg_m^T + bg_m) (n x 192, ldg);  P = [E * g_v | E * g_t | E * g_f]  (n x 192, ldp)
+ *   S = [A | B] (n x 128, ldsp) is what the backward reads.
+ * spectrum_bwd from dP (n x 192): dE (+)= sum_m dP_m * g_m (accumulate = 1 adds to dE); z (n x 192) = dP_m * E * g_m
+ * (1 - g_m), the gate pre-activation rows (host side: dWg_m = z_m^T conv_m, dbg_m = colsum(z_m)); dV, dT (lddv); and
+ * the filter gradients dWi, dWt, dWf (33 x 2 each): per-tile column sums go to ws (gmr_smore_spectrum_ws_floats(n)
+ * floats) and a second pass (a workgroup per filter) adds them in a fixed fp64 order that does not depend on the grid. */
+int32_t gmr_smore_tile_rows(void);
+int32_t gmr_smore_max_blocks(void);
+int64_t gmr_smore_spectrum_ws_floats(int64_t n);
+int gmr_smore_twiddles(float* fwd, float* inv, void* stream);
+int gmr_smore_spectrum_fwd(int64_t n, const float* V, int64_t ldv, const float* T, int64_t ldt, const float* E,
+                           int64_t lde, const float* Wi, const float* Wt, const float* Wf, const float* Wgv,
+                           const float* bgv, const float* Wgt, const float* bgt, const float* Wgf, const float* bgf,
+                           int64_t ldw, float* S, int64_t ldsp, float* conv, int64_t ldcv, float* g, int64_t ldg,
+                           float* P, int64_t ldp, void* stream);
+int gmr_smore_spectrum_bwd(int64_t n, const float* dP, int64_t lddp, const float* g, int64_t ldg, const float* E,
+                           int64_t lde, const float* S, int64_t ldsp, const float* Wi, const float* Wt,
+                           const float* Wf, const float* Wgv, const float* Wgt, const float* Wgf, int64_t ldw,
+                           float* dE, int64_t ldde, int32_t accumulate, float* z, int64_t ldz, float* dV, float* dT,
+                           int64_t lddv, float* ws, int64_t ws_floats, float* dWi, float* dWt, float* dWf,
+                           void* stream);
+/* Fuser over the n = U + I rows of abf = [a | b | f] (n x 192, ldabf) and c (ldc):
+ *   hv = tanh(Wv1 f + bv1), sv = softmax_64(Wv2 hv);  ht, st the same from Wt1, bt1, Wt2
+ *   gi, gt, gf = keep * sigmoid(W. c + b.) / (1 - p);  side = (gi sv a + gt st b + gf f) / 3;  all = c + side
+ * drop_mode 0: no dropout (also whenever p = 0); 1: keep (n x 192 bytes, ldk, [image | text | fusion], non-zero =
+ * kept) is given; 2: drawn from Philox keyed on (seed, the gate's site, step, row, column group), so a row's mask does
+ * not depend on the tiling.  saved (n x 448, lds) = [hv | ht | sv | st | gi | gt | gf] with the masked gate rows.
+ * Backward from dall, dside, dcin as gmr_mgcn_fuse_bwd (p: the forward's, 0 where it dropped nothing): dabf =
+ * [da | db | df] (n x 192), dc, and z (n x 448, ldz) = [z1v | z2v | z1t | z2t | zi | zt | zf], the pre-activation rows
+ * of the seven products.  Host side: dWv1 = z1v^T f, dbv1 = colsum(z1v), dWv2 = z2v^T hv, the same for t;
+ * dWi = zi^T c, dbi = colsum(zi), the same for Wt, Wf. */
+int gmr_smore_fuse_fwd(int64_t n, const float* abf, int64_t ldabf, const float* c, int64_t ldc, const float* Wv1,
+                       const float* bv1, const float* Wv2, const float* Wt1, const float* bt1, const float* Wt2,
+                       const float* Wi, const float* bi, const float* Wt, const float* bt, const float* Wf,
+                       const float* bf, int64_t ldw, float p, int32_t drop_mode, const uint8_t* keep, int64_t ldk,
+                       uint64_t seed, uint64_t step, float* side, float* all, int64_t ldo, float* saved, int64_t lds,
+                       void* stream);
+int gmr_smore_fuse_bwd(int64_t n, const float* dall, int64_t ldda, const float* dside, const float* dcin, int64_t ldds,
+                       const float* abf, int64_t ldabf, const float* saved, int64_t lds, float p, const float* Wv1,
+                       const float* Wv2, const float* Wt1, const float* Wt2, const float* Wi, const float* Wt,
+                       const float* Wf, int64_t ldw, float* dabf, int64_t lddabf, float* dc, int64_t lddc, float* z,
+                       int64_t ldz, void* stream);
+
 /* (Round 5's native executor of a captured HIP graph, gmr_graph_exec_*, was removed in round 6: its replayed
  * step ran slower on the GPU than eager issue; the host tape of gmr/tape.py removes the Python issue cost and
  * keeps the eager streams and order.) */
