@@ -39,7 +39,8 @@ __device__ __forceinline__ void softmax2(const float* mw, float& w0, float& w1) 
 
 // normalize backward of one 64-column row held by 16 lanes (4 columns each): (g - y <y,g>) / nrm, the projection
 // term dropped when the norm was clamped, then the leaky-ReLU backward on sign(y) (slope 1: none); the
-// expression of normalize_bwd_kernel, so the fused callers give its bits
+// expression of normalize_bwd_kernel, so a fused caller that stores the value gives its bits (assemble_kernel).
+// One that adds it to memory need not: the compiler fuses the 1 / nrm scaling into that add
 __device__ __forceinline__ float4 nbwd_leaky(float4 g, float4 y, float nv, float slope) {
   float dp = row16_sum(dot4(y, g));
   if (nv <= 1e-12f) dp = 0.f;
@@ -179,7 +180,8 @@ __device__ __forceinline__ void bpr_rows(int gid, int B, int64_t U, const float*
   if (!ok) return;
   float s = 1.f / (1.f + expf(-x));
   float gx = -(s * (1.f - s)) / (1e-10f + s) * inv_norm;  // inv_norm = 1 / rows of the (global) batch
-  if ((gid & 15) == 0) loss[b] = -logf(1e-10f + s);
+  // (the log of a row in double: the device's logf is 1.7 ulp off at 1e-10f, the loss of a row with s = 0)
+  if ((gid & 15) == 0) loss[b] = -(float)log((double)(1e-10f + s));
   st4(contrib + (int64_t)b * 64 + c, gmr::f4_scale(gx, sub4(p, q)));
   st4(contrib + ((int64_t)B + b) * 64 + c, gmr::f4_scale(gx, a));
   st4(contrib + (2 * (int64_t)B + b) * 64 + c, gmr::f4_scale(-gx, a));
@@ -208,7 +210,9 @@ __global__ void __launch_bounds__(256) row_softmax_kernel(int64_t rows, int64_t 
   const float S = (red[0] + red[1]) + (red[2] + red[3]);
   const float k = coef / S;
   for (int64_t j = threadIdx.x; j < cols; j += 256) p[j] = k * expf(p[j]);
-  if (threadIdx.x == 0) lse[r] = logf(S);
+  // one log a row, taken in double: the device's logf is up to 2.3 ulp off at these S (its log2 instruction's one
+  // ulp, scaled), several times the error of S itself
+  if (threadIdx.x == 0) lse[r] = (float)log((double)S);
 }
 
 // contrastive per-row terms for a gathered batch.  For row b with node t_b:
@@ -290,6 +294,9 @@ __global__ void scatter_sorted_kernel(int n, int cols, const unsigned long long*
 // taken through the normalize backward of each 64-column view (y = CLN, nrm = [nrm_img | nrm_txt] per node) and
 // added to dK: dK[key] += nbwd([s_img | s_txt]).  The normalize backward is linear in its input, so adding
 // nbwd(sparse part) to the table pass's nbwd(dense part) (cl_table_reduce_nbwd_kernel) gives nbwd of the sum.
+// Against scatter_sorted_kernel into zeros followed by normalize_bwd_kernel(accumulate = 1): the same bits onto a
+// zero dK; onto anything else the last step here is one fused multiply-add, dK + (1 / nrm) (s - y <y, s>), where
+// the two launches round the product and then the sum (one rounding more; both hold the fp64 bar of the tests).
 __global__ void scatter_sorted_nbwd_kernel(int n, const unsigned long long* __restrict__ plan,
                                            const float* __restrict__ contrib, int64_t ldc,
                                            const float* __restrict__ y, const float* __restrict__ nrm, int64_t nn,
