@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "gmr_common.h"
+#include "x6_split.h"
 
 namespace {
 
@@ -1273,16 +1274,24 @@ constexpr int kC6B = 40;                              // bf16 row stride, transp
 constexpr int kC6PA = 32 * kC6A, kC6PB = 64 * kC6B;   // bf16 elements per plane
 constexpr int kC6Stage = 3 * (kC6PA + kC6PB);         // bf16 elements per staged block
 
+// The splits are spelled out as single-issue VALU instructions, a pair of elements per asm block (x6_split.h):
+// written in C++ the compiler packs the subtractions of neighbours, and with them the scale and weight
+// arithmetic around the exp, into v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32, each ~13 cycles dearer than two
+// scalar instructions beside v_mfma_f32_32x32x16_bf16 (profiles/x6_split_listing_counts.txt).  Same
+// values, same roundings, same bits.
+typedef unsigned c6u4 __attribute__((ext_vector_type(4)));
+
 __device__ __forceinline__ void c6_split8(const float (&v)[8], c6bf8 (&o)[3]) {
+  c6u4 h, m, l;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const __bf16 hh = (__bf16)__builtin_amdgcn_fmed3f(v[e], -0x1.fep127f, 0x1.fep127f);
-    const float r1 = v[e] - (float)hh;  // exact
-    const __bf16 mm = (__bf16)r1;
-    o[0][e] = hh;
-    o[1][e] = mm;
-    o[2][e] = (__bf16)(r1 - (float)mm);  // exact
+  for (int e = 0; e < 4; ++e) {
+    unsigned a, b, c;
+    gmr_x6::split_pair(v[2 * e], v[2 * e + 1], a, b, c);
+    h[e] = a, m[e] = b, l[e] = c;
   }
+  o[0] = __builtin_bit_cast(c6bf8, h);
+  o[1] = __builtin_bit_cast(c6bf8, m);
+  o[2] = __builtin_bit_cast(c6bf8, l);
 }
 
 // Y products (E T over the staged block) keep three of the six: hi*hi + hi*mid + mid*hi.  The dropped terms are
@@ -1290,12 +1299,30 @@ __device__ __forceinline__ void c6_split8(const float (&v)[8], c6bf8 (&o)[3]) {
 // (<= 1.2e-5 of sum |e t| worst case) for the gradients it feeds (dP, dT: the parity tests' 1e-4 bars); the
 // logits S, which feed exp and the loss rows (1e-5), keep all six (round 6: 48 -> 36 MFMAs per staged block)
 __device__ __forceinline__ void c6_split8_2(const float (&v)[8], c6bf8 (&o)[2]) {
+  c6u4 h, m;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const __bf16 hh = (__bf16)__builtin_amdgcn_fmed3f(v[e], -0x1.fep127f, 0x1.fep127f);
-    o[0][e] = hh;
-    o[1][e] = (__bf16)(v[e] - (float)hh);
+  for (int e = 0; e < 4; ++e) {
+    unsigned a, b;
+    gmr_x6::split_pair2(v[2 * e], v[2 * e + 1], a, b);
+    h[e] = a, m[e] = b;
   }
+  o[0] = __builtin_bit_cast(c6bf8, h);
+  o[1] = __builtin_bit_cast(c6bf8, m);
+}
+// the same of the weighted E of the table pass, v = w * x: the remainder is fma(w, x, -hi), what the compiler
+// contracts (w * x) - hi to (the product's rounding error goes into mid: closer to w x, and the bits every
+// earlier build of this pass gave)
+__device__ __forceinline__ void c6_split8_2w(const float (&v)[8], const float (&w)[8], const float (&x)[8],
+                                             c6bf8 (&o)[2]) {
+  c6u4 h, m;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    unsigned a, b;
+    gmr_x6::split_pair2_fma(v[2 * e], v[2 * e + 1], w[2 * e], x[2 * e], w[2 * e + 1], x[2 * e + 1], a, b);
+    h[e] = a, m[e] = b;
+  }
+  o[0] = __builtin_bit_cast(c6bf8, h);
+  o[1] = __builtin_bit_cast(c6bf8, m);
 }
 // fp32 block (32 x 64, stride kClLd) -> the three row-major and the three transposed bf16 planes
 __device__ __forceinline__ void c6_convert(const float* sf, __bf16* stg) {
@@ -1438,13 +1465,15 @@ __global__ void __launch_bounds__(256, 2) cl6_kernel(int nf, int ns, const float
       for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const c6bf8*>(A + p * kC6PA + l32 * kC6A + 16 * k + 8 * h);
       sacc = c6_mfma6(a, fr[k], sacc);
     }
-    float ev[16];
+    float ev[16], wv[16], xv[16];  // TABLE: ev = wv * xv
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int r = (e & 3) + 8 * (e >> 2) + 4 * h;
       const float x = j + r < s1 ? cl_exp<FAST>(inv_t, sacc[e]) : 0.f;
       if (TABLE) {
-        ev[e] = s_w[cur][r] * x;
+        wv[e] = s_w[cur][r];
+        xv[e] = x;
+        ev[e] = wv[e] * x;
       } else {
         ev[e] = x;
         z += x;
@@ -1456,7 +1485,14 @@ __global__ void __launch_bounds__(256, 2) cl6_kernel(int nf, int ns, const float
       const float evs[8] = {ev[8 * t2], ev[8 * t2 + 1], ev[8 * t2 + 2], ev[8 * t2 + 3],
                             ev[8 * t2 + 4], ev[8 * t2 + 5], ev[8 * t2 + 6], ev[8 * t2 + 7]};
       c6bf8 eb[2], a0[2], a1[2];
-      c6_split8_2(evs, eb);
+      if constexpr (TABLE) {
+        float ws8[8], xs8[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) ws8[q] = wv[8 * t2 + q], xs8[q] = xv[8 * t2 + q];
+        c6_split8_2w(evs, ws8, xs8, eb);
+      } else {
+        c6_split8_2(evs, eb);
+      }
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
         a0[p] = *reinterpret_cast<const c6bf8*>(Bt + p * kC6PB + l32 * kC6B + 8 * (2 * t2 + h));
@@ -1564,13 +1600,15 @@ __global__ void __launch_bounds__(256, 2) cl6p_kernel(int nf, int ns, const floa
     const __bf16* A = s_stg + cur * kC6Stage;
     clx16 snext;
     if (more) snext = sprod(s_stg + (cur ^ 1) * kC6Stage);  // the matrix pipe's next S ...
-    float ev[16];  // ... while this block's logits are exponentiated
+    float ev[16], wv[16], xv[16];  // ... while this block's logits are exponentiated (TABLE: ev = wv * xv)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int r = (e & 3) + 8 * (e >> 2) + 4 * h;
       const float x = j + r < s1 ? cl_exp<FAST>(inv_t, scur[e]) : 0.f;
       if (TABLE) {
-        ev[e] = s_w[cur][r] * x;
+        wv[e] = s_w[cur][r];
+        xv[e] = x;
+        ev[e] = wv[e] * x;
       } else {
         ev[e] = x;
         z += x;
@@ -1582,7 +1620,14 @@ __global__ void __launch_bounds__(256, 2) cl6p_kernel(int nf, int ns, const floa
       const float evs[8] = {ev[8 * t2], ev[8 * t2 + 1], ev[8 * t2 + 2], ev[8 * t2 + 3],
                             ev[8 * t2 + 4], ev[8 * t2 + 5], ev[8 * t2 + 6], ev[8 * t2 + 7]};
       c6bf8 eb[2], a0[2], a1[2];
-      c6_split8_2(evs, eb);
+      if constexpr (TABLE) {
+        float ws8[8], xs8[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) ws8[q] = wv[8 * t2 + q], xs8[q] = xv[8 * t2 + q];
+        c6_split8_2w(evs, ws8, xs8, eb);
+      } else {
+        c6_split8_2(evs, eb);
+      }
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
         a0[p] = *reinterpret_cast<const c6bf8*>(Bt + p * kC6PB + l32 * kC6B + 8 * (2 * t2 + h));

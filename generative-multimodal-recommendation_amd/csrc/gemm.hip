@@ -462,11 +462,11 @@ int stages64() {
 template <int BM, int BN, int WGM, int WGN, bool AKC, bool BKC, int MF>
 int launch_t(bool vec, bool glds, dim3 grid, hipStream_t st, int64_t M, int64_t N, int64_t K, const float* A,
               int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, const Epi& epi, int tiles_n,
-              int64_t kps, float* ws, int* counters) {
+              int64_t kps, float* ws, int* counters, bool x6p) {
   const dim3 blk(64 * WGM * WGN);
   if constexpr (MF == 6) {  // split-bf16 kernel (gemm_x6.hip): NT products, 16-byte aligned (make_plan)
     // -1: no split-bf16 kernel for this tile / operand layout (the caller reports GMR_ERR_ARG)
-    return x6_launch(BM, BN, grid, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps, ws, AKC, BKC);
+    return x6_launch(BM, BN, grid, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps, ws, AKC, BKC, x6p);
   } else {
   if constexpr (MF == 32) {
     if (vec && glds) {
@@ -495,35 +495,35 @@ int launch_t(bool vec, bool glds, dim3 grid, hipStream_t st, int64_t M, int64_t 
 template <int BM, int BN, int WGM, int WGN, int MF>
 int launch_mf(int ta, int tb, bool vec, bool glds, dim3 grid, hipStream_t st, int64_t M, int64_t N, int64_t K,
                const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, const Epi& epi,
-               int tiles_n, int64_t kps, float* ws, int* counters) {
+               int tiles_n, int64_t kps, float* ws, int* counters, bool x6p) {
   // AKC = A is k-contiguous (not transposed); BKC = B is k-contiguous (transposed)
   if (!ta && tb)
     return launch_t<BM, BN, WGM, WGN, true, true, MF>(vec, glds, grid, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps,
-                                               ws, counters);
+                                               ws, counters, x6p);
   else if (!ta && !tb)
     return launch_t<BM, BN, WGM, WGN, true, false, MF>(vec, glds, grid, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps,
-                                                ws, counters);
+                                                ws, counters, x6p);
   else if (ta && !tb)
     return launch_t<BM, BN, WGM, WGN, false, false, MF>(vec, glds, grid, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n,
-                                                 kps, ws, counters);
+                                                 kps, ws, counters, x6p);
   else
     return launch_t<BM, BN, WGM, WGN, false, true, MF>(vec, glds, grid, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps,
-                                                ws, counters);
+                                                ws, counters, x6p);
 }
 
 template <int BM, int BN, int WGM, int WGN>
 int launch_tile(int mf, bool glds, int ta, int tb, bool vec, dim3 grid, hipStream_t st, int64_t M, int64_t N,
                  int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
-                 const Epi& epi, int tiles_n, int64_t kps, float* ws, int* counters) {
+                 const Epi& epi, int tiles_n, int64_t kps, float* ws, int* counters, bool x6p) {
   if (mf == 6)
     return launch_mf<BM, BN, WGM, WGN, 6>(ta, tb, vec, false, grid, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps, ws,
-                                   counters);
+                                   counters, x6p);
   else if (mf == 16)
     return launch_mf<BM, BN, WGM, WGN, 16>(ta, tb, vec, false, grid, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps,
-                                    ws, counters);
+                                    ws, counters, x6p);
   else
     return launch_mf<BM, BN, WGM, WGN, 32>(ta, tb, vec, glds, grid, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps,
-                                    ws, counters);
+                                    ws, counters, x6p);
 }
 
 // Tile, MFMA shape and split-K choice of gmr_gemm_f32 (tile / split_k = 0: automatic).
@@ -537,6 +537,7 @@ struct Plan {
   bool glds;
   int64_t tm, tn, kps;
   int xpose;  // split-bf16 plans of TN / NN / TT calls: 1 = A, 2 = B copied k-contiguous into the workspace
+  bool x6p;   // split-bf16 plans: the pipelined k loop (gemm_x6.hip PIPE 1)
 };
 
 int default_mfma() {
@@ -611,7 +612,9 @@ Plan make_plan_core(int ta, int tb, int64_t M, int64_t N, int64_t K, int tile, i
   const bool x6 = allow_x6 && ((tile & GMR_GEMM_X6) || default_x6()) &&
                   !(tile & (GMR_GEMM_F32 | GMR_GEMM_MFMA16 | GMR_GEMM_MFMA32 | GMR_GEMM_GLDS | GMR_GEMM_REGSTAGE));
   const bool x6_64 = x6 && ((tile & GMR_GEMM_X6) || default_x6_64());
-  tile &= ~(GMR_GEMM_MFMA16 | GMR_GEMM_MFMA32 | GMR_GEMM_GLDS | GMR_GEMM_REGSTAGE | GMR_GEMM_X6 | GMR_GEMM_F32);
+  const bool x6_pipe1 = tile & GMR_GEMM_X6_PIPE1;
+  tile &= ~(GMR_GEMM_MFMA16 | GMR_GEMM_MFMA32 | GMR_GEMM_GLDS | GMR_GEMM_REGSTAGE | GMR_GEMM_X6 | GMR_GEMM_F32 |
+            GMR_GEMM_X6_PIPE1);
   if (tile == 0) {
     // measured on MI355X (scripts/gemm_bench.py): 256^2 tiles win the long-K products of the
     // denoiser (M >= 2048, N >= 1000, K >= 4096; one 16-wave block per CU), 128^2 the wide
@@ -695,6 +698,7 @@ Plan make_plan_core(int ta, int tb, int64_t M, int64_t N, int64_t K, int tile, i
   p.splits = (int)((K + kps - 1) / kps);
   p.kps = kps;
   p.xpose = 0;
+  p.x6p = mf == 6 && x6_pipe1;
   return p;
 }
 
@@ -776,7 +780,7 @@ extern "C" int gmr_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t M, int64_t
   GMR_ARG(epilogue != GMR_EPI_ROWSCALE_AUX || rowvec1, "epilogue needs rowvec1");
   {
     const int t = tile & ~(GMR_GEMM_MFMA16 | GMR_GEMM_MFMA32 | GMR_GEMM_GLDS | GMR_GEMM_REGSTAGE | GMR_GEMM_X6 |
-                           GMR_GEMM_F32);
+                           GMR_GEMM_F32 | GMR_GEMM_X6_PIPE1);
     GMR_ARG(t == 0 || t == 64 || t == 128 || t == 256 || t == 256128 || t == 128256 || t == 12864,
             "tile must be 0 (auto), 64, 128, 256, 256128, 128256 or 12864 (| GMR_GEMM_MFMA16 / GMR_GEMM_MFMA32)");
   }
@@ -847,22 +851,22 @@ extern "C" int gmr_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t M, int64_t
   int lrc = 0;
   switch (tile) {
     case 256:
-      lrc = launch_tile<256, 256, 4, 4>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters);
+      lrc = launch_tile<256, 256, 4, 4>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters, pl.x6p);
       break;
     case 256128:
-      lrc = launch_tile<256, 128, 4, 2>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters);
+      lrc = launch_tile<256, 128, 4, 2>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters, pl.x6p);
       break;
     case 128256:
-      lrc = launch_tile<128, 256, 2, 4>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters);
+      lrc = launch_tile<128, 256, 2, 4>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters, pl.x6p);
       break;
     case 12864:
-      lrc = launch_tile<128, 64, 2, 2>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters);
+      lrc = launch_tile<128, 64, 2, 2>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters, pl.x6p);
       break;
     case 128:
-      lrc = launch_tile<128, 128, 2, 2>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters);
+      lrc = launch_tile<128, 128, 2, 2>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters, pl.x6p);
       break;
     default:
-      lrc = launch_tile<64, 64, 2, 2>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters);
+      lrc = launch_tile<64, 64, 2, 2>(pl.mf, pl.glds, trans_a, trans_b, vec, grid, st, M, N, K, A, lda, B, ldb, C, ldc, e, tnp, kps, ws, counters, pl.x6p);
   }
   GMR_ARG(lrc == 0, "no split-bf16 kernel for this tile and operand layout");
   GMR_LAUNCHED();

@@ -369,7 +369,7 @@ int x6_ring();  // gemm_x6.hip: the register-ring 64^2 split-bf16 kernel is on (
 int x6_inplace();  // gemm_x6.hip: TN / NN operands read in place, no transposed copies (GMR_X6_INPLACE, default 0: opt-in, measured slower)
 int x6_launch(int bm, int bn, dim3 grid, hipStream_t st, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
               const float* B, int64_t ldb, float* C, int64_t ldc, const Epi& epi, int tiles_n, int64_t kps, float* ws,
-              bool akc = true, bool bkc = true);
+              bool akc = true, bool bkc = true, bool pipe = false);  // pipe: the plan asks for the pipelined k loop
 
 // dst[c * ld_dst + r] = src[r * ld_src + c] for r < rows, c < cols (the k-contiguous copy of an m- or
 // n-contiguous operand for the split-bf16 kernel)

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "gemm_impl.h"
+#include "x6_split.h"
 
 namespace {
 using namespace gmr_gemm;
@@ -40,6 +41,23 @@ __device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l)
   l = (__bf16)(r1 - (float)m);    // exact: at most 8 significand bits remain
 }
 
+// N (even) consecutive elements -> their three bf16 vectors, pair by pair as single-issue instructions (x6_split.h:
+// split3's values and roundings; written in C++ the subtractions of neighbours compile to v_pk_add_f32)
+template <int N, typename V>
+__device__ __forceinline__ void split3n(const float* v, V& h, V& m, V& l) {
+  typedef unsigned U __attribute__((ext_vector_type(N / 2)));
+  U hh, mm, ll;
+#pragma unroll
+  for (int e = 0; e < N / 2; ++e) {
+    unsigned a, b, c;
+    gmr_x6::split_pair(v[2 * e], v[2 * e + 1], a, b, c);
+    hh[e] = a, mm[e] = b, ll[e] = c;
+  }
+  h = __builtin_bit_cast(V, hh);
+  m = __builtin_bit_cast(V, mm);
+  l = __builtin_bit_cast(V, ll);
+}
+
 // register tile -> the three bf16 planes of one LDS stage (plane stride PL elements)
 template <int R, bool KC, int NT, int N4>
 __device__ __forceinline__ void x6_store(const float4 (&r)[N4], __bf16* s) {
@@ -52,14 +70,7 @@ __device__ __forceinline__ void x6_store(const float4 (&r)[N4], __bf16* s) {
     if (KC) {  // 4 consecutive k of one row: 8 bytes per plane
       const int rr = idx / (BK / 4), k4 = (idx % (BK / 4)) * 4;
       bf16x4 h, m, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        __bf16 a, b, c;
-        split3(v[e], a, b, c);
-        h[e] = a;
-        m[e] = b;
-        l[e] = c;
-      }
+      split3n<4>(v, h, m, l);
       const int off = rr * BK + (((k4 >> 3) ^ x6_swz(rr)) << 3) + (k4 & 7);
       *reinterpret_cast<bf16x4*>(s + off) = h;
       *reinterpret_cast<bf16x4*>(s + PL + off) = m;
@@ -156,14 +167,7 @@ struct MnTile {
 #pragma unroll
     for (int c = 0; c < E / 8; ++c) {
       bf16x8 h, m, l;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        __bf16 a, b, d;
-        split3(v[8 * c + e], a, b, d);
-        h[e] = a;
-        m[e] = b;
-        l[e] = d;
-      }
+      split3n<8>(v + 8 * c, h, m, l);
       const int o = rr * BK + ((((kt >> 3) + c) ^ x6_swz(rr)) << 3);
       *reinterpret_cast<bf16x8*>(s + o) = h;
       *reinterpret_cast<bf16x8*>(s + PL + o) = m;
@@ -171,32 +175,6 @@ struct MnTile {
     }
   }
 };
-
-// NT products (A [M][K], B [N][K], both k-contiguous, 16-byte aligned, lda / ldb multiples of 4)
-// float4 granules [I0, I1) of a k-contiguous register tile -> the three bf16 planes (as x6_store)
-template <int R, int NT, int N4, int I0, int I1>
-__device__ __forceinline__ void x6_store_part(const float4 (&r)[N4], __bf16* s) {
-  constexpr int PL = R * BK;
-#pragma unroll
-  for (int i = I0; i < I1; ++i) {
-    const int idx = threadIdx.x + NT * i;
-    const int rr = idx / (BK / 4), k4 = (idx % (BK / 4)) * 4;
-    const float v[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
-    bf16x4 h, m, l;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      __bf16 a, b, c;
-      split3(v[e], a, b, c);
-      h[e] = a;
-      m[e] = b;
-      l[e] = c;
-    }
-    const int off = rr * BK + (((k4 >> 3) ^ x6_swz(rr)) << 3) + (k4 & 7);
-    *reinterpret_cast<bf16x4*>(s + off) = h;
-    *reinterpret_cast<bf16x4*>(s + PL + off) = m;
-    *reinterpret_cast<bf16x4*>(s + 2 * PL + off) = l;
-  }
-}
 
 // one k tile of a k-contiguous operand straight into ring registers d (KcTile's offsets; full tile or the
 // zero-padded last one): the loads of later ring slots stay in flight while earlier slots are split
@@ -219,20 +197,6 @@ __device__ __forceinline__ void kc_fetch(float4 (&d)[N4], const KcTile<R, NT>& t
       }
       d[i] = v;
     }
-  }
-}
-
-// instruction order of one pipelined MFMA step: its NR fragment reads, then NM MFMAs, each followed
-// by NV VALU instructions of the next tile's split and, for the first NW, one of its LDS writes
-// (sched_group_barrier masks: 0x008 MFMA, 0x002 VALU, 0x100 DS read, 0x200 DS write)
-template <int NR, int NM, int NV, int NW>
-__device__ __forceinline__ void x6_interleave() {
-  __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-#pragma unroll
-  for (int i = 0; i < NM; ++i) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x002, NV, 0);
-    if (i < NW) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
   }
 }
 
@@ -282,8 +246,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN, OCC) gemm_x6_kernel(int64_t M,
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = sml[i][j][e] = 0.f;
 
-  // one 16-deep MFMA step s (k = 16 s + 8 h + j: chunk 2 s + h of the 32-deep rows) of a stage
-  auto mstep = [&](const __bf16* a_s, int s) {
+  // one 16-deep MFMA step s (k = 16 s + 8 h + j: chunk 2 s + h of the 32-deep rows) of a stage; gap(g) is called
+  // after the step's g-th MFMA (the pipelined loop puts a piece of the next tile's split there)
+  auto mstep = [&](const __bf16* a_s, int s, auto&& gap) {
     const __bf16* b_s = a_s + 3 * APL;
     bf16x8 fb[3][TN];
 #pragma unroll
@@ -293,25 +258,44 @@ __global__ void __launch_bounds__(64 * WGM * WGN, OCC) gemm_x6_kernel(int64_t M,
 #pragma unroll
       for (int p = 0; p < 3; ++p) fb[p][j] = *reinterpret_cast<const bf16x8*>(b_s + p * BPL + off);
     }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {  // A fragments read per row block: 12 live registers, not 12 TM
-      bf16x8 fa[3];
+    // A fragments read per row block: 12 live registers, not 12 TM; the pipelined loop (one block per CU) reads
+    // them all ahead of the step's first MFMA, since nothing moves across its gaps
+    bf16x8 fa_[TM][3];
+    auto read_a = [&](int i) {
       const int row = wm * WTM + i * 32 + l32;
       const int off = row * BK + (((2 * s + h) ^ x6_swz(row)) << 3);
 #pragma unroll
-      for (int p = 0; p < 3; ++p) fa[p] = *reinterpret_cast<const bf16x8*>(a_s + p * APL + off);
+      for (int p = 0; p < 3; ++p) fa_[i][p] = *reinterpret_cast<const bf16x8*>(a_s + p * APL + off);
+    };
+    if constexpr (PIPE == 1) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i) read_a(i);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      if constexpr (PIPE != 1) read_a(i);
+      const bf16x8(&fa)[3] = fa_[i];
 #pragma unroll
       for (int j = 0; j < TN; ++j) {  // small terms first
+        const int g = 6 * (i * TN + j);
         sml[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[1][j], sml[i][j], 0, 0, 0);
+        gap(g);
         sml[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[2][j], sml[i][j], 0, 0, 0);
+        gap(g + 1);
         sml[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[0][j], sml[i][j], 0, 0, 0);
+        gap(g + 2);
         sml[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[1][j], sml[i][j], 0, 0, 0);
+        gap(g + 3);
         sml[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[0][j], sml[i][j], 0, 0, 0);
+        gap(g + 4);
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0][j], acc[i][j], 0, 0, 0);
+        gap(g + 5);
       }
     }
   };
 
+  auto nogap = [](int) {};
   static_assert((AKC && BKC) || PIPE == 0, "m- / n-contiguous operands: the PIPE 0 loop only");
   std::conditional_t<AKC, KcTile<BM, NT>, MnTile<BM, NT>> ra;
   std::conditional_t<BKC, KcTile<BN, NT>, MnTile<BN, NT>> rb;
@@ -377,8 +361,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN, OCC) gemm_x6_kernel(int64_t M,
           x6_store<BN, true, NT>(qb[q], buf + 3 * APL);
           __syncthreads();
           fetch_slot(qa[q], qb[q], t + PF);
-          mstep(buf, 0);
-          mstep(buf, 1);
+          mstep(buf, 0, nogap);
+          mstep(buf, 1, nogap);
         }
       }
     }
@@ -394,8 +378,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN, OCC) gemm_x6_kernel(int64_t M,
     const bool more = t + 1 < nk;
     if (more) fetch(t + 1);
     const __bf16* a_s = smem + cur * STAGE;
-    mstep(a_s, 0);
-    mstep(a_s, 1);
+    mstep(a_s, 0, nogap);
+    mstep(a_s, 1, nogap);
     if constexpr (NBUF == 2) {
       if (more) store(smem + (cur ^ 1) * STAGE);
       __syncthreads();
@@ -407,12 +391,20 @@ __global__ void __launch_bounds__(64 * WGM * WGN, OCC) gemm_x6_kernel(int64_t M,
     }
   }
   } else {
-    // PIPE = 1 (NBUF = 2): registers double-buffered; tile t+2 loads while tile t is computed and
-    // tile t+1 (landed during t-1) is split into the free LDS buffer BETWEEN the MFMAs of tile t
-    // (one basic block per step, x6_interleave orders it).  The split runs unconditionally: on the
-    // last tile it fills the idle buffer with stale registers that are never read.
+    // PIPE = 1 (NBUF = 2): registers double-buffered; tile t+2 loads while tile t is computed and tile t+1
+    // (landed during t-1) is split into the free LDS buffer BETWEEN the MFMAs of tile t.  The placement is by
+    // hand: the split of a pair of elements is three pieces of 4 + 4 + 5 single-issue VALU instructions
+    // (x6_split.h), piece after piece goes behind successive MFMAs, and a sched_barrier after every gap keeps the
+    // compiler from moving anything across (it ignored sched_group_barrier pipelines here and left the whole
+    // split in one burst between the two steps: profiles/x6_split_listing_counts.txt).  A 32-cycle
+    // v_mfma_f32_32x32x16_bf16 gap hides five 4-cycle fillers, so at most one piece (and one LDS write) per gap
+    // where the tile has the gaps for it: 128^2, 48 pieces in 48 gaps; 256 x 128, 36 in 48.  The split runs
+    // unconditionally: on the last tile it fills the idle buffer with stale registers that are never read.
     static_assert(NBUF == 2, "the pipelined loop double-buffers LDS");
-    constexpr int NA = KcTile<BM, NT>::N4, NB = KcTile<BN, NT>::N4, NF = NA + NB, H0 = (NF + 1) / 2;
+    constexpr int NA = KcTile<BM, NT>::N4, NB = KcTile<BN, NT>::N4, NF = NA + NB;
+    constexpr int NM = 6 * TM * TN;                        // MFMAs (gaps) per step
+    constexpr int NPC = 6 * NF;                            // pieces per k tile: 2 pairs per float4 granule
+    constexpr int PPG = (NPC + 2 * NM - 1) / (2 * NM);     // pieces per gap
     float4 qa[NA], qb[NB];  // tile t+1 while ra / rb take tile t+2
     auto fetch_next = [&](int t) {  // registers of tile t (clamped: past the end a tile is re-read)
       fetch(min(t, nk - 1));
@@ -432,23 +424,38 @@ __global__ void __launch_bounds__(64 * WGM * WGN, OCC) gemm_x6_kernel(int64_t M,
       if (t + 2 < nk) fetch_next(t + 2);
       const __bf16* a_s = smem + (t & 1) * STAGE;
       __bf16* nxt = smem + ((t & 1) ^ 1) * STAGE;
-      // granules [0, H0) of the A|B register list go with step 0, the rest with step 1
-      mstep(a_s, 0);
-      if constexpr (H0 <= NA) {
-        x6_store_part<BM, NT, NA, 0, H0>(qa, nxt);
-      } else {
-        x6_store_part<BM, NT, NA, 0, NA>(qa, nxt);
-        x6_store_part<BN, NT, NB, 0, H0 - NA>(qb, nxt + 3 * APL);
-      }
-      x6_interleave<6 * (TM + TN), 6 * TM * TN, 3, 3 * H0>();
-      mstep(a_s, 1);
-      if constexpr (H0 <= NA) {
-        x6_store_part<BM, NT, NA, H0, NA>(qa, nxt);
-        x6_store_part<BN, NT, NB, 0, NB>(qb, nxt + 3 * APL);
-      } else {
-        x6_store_part<BN, NT, NB, H0 - NA, NB>(qb, nxt + 3 * APL);
-      }
-      x6_interleave<6 * (TM + TN), 6 * TM * TN, 3, 3 * (NF - H0)>();
+      gmr_x6::Pair ps[2 * NF];
+      unsigned lo[2 * NF];
+      // piece c of the tile: pair c / 3 (granule c / 6 of the A | B register list, its .xy or .zw), phase c % 3;
+      // the second pair of a granule writes plane (phase) of the granule once both pairs have it
+      auto piece = [&](int c) {
+        const int p = c / 3, ph = c % 3, gr = p >> 1;
+        const float4 v = gr < NA ? qa[gr < NA ? gr : 0] : qb[gr < NA ? 0 : gr - NA];
+        const float x0 = (p & 1) ? v.z : v.x, x1 = (p & 1) ? v.w : v.y;
+        if (ph == 0) gmr_x6::split_p0(x0, x1, ps[p]);
+        else if (ph == 1) gmr_x6::split_p1(x0, x1, ps[p]);
+        else lo[p] = gmr_x6::split_p2(ps[p]);
+        if (p & 1) {
+          const bool isa = gr < NA;
+          const int idx = threadIdx.x + NT * (isa ? gr : gr - NA);
+          const int rr = idx / (BK / 4), k4 = (idx % (BK / 4)) * 4;
+          const int off = rr * BK + (((k4 >> 3) ^ x6_swz(rr)) << 3) + (k4 & 7);
+          __bf16* pl = nxt + (isa ? 0 : 3 * APL) + ph * (isa ? APL : BPL) + off;
+          const uint2 w = ph == 0   ? make_uint2(ps[p - 1].h, ps[p].h)
+                          : ph == 1 ? make_uint2(ps[p - 1].m, ps[p].m)
+                                    : make_uint2(lo[p - 1], lo[p]);
+          *reinterpret_cast<uint2*>(pl) = w;
+        }
+      };
+      auto gap0 = [&](int g) {
+#pragma unroll
+        for (int c = g * PPG; c < (g + 1) * PPG; ++c)
+          if (c < NPC) piece(c);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      auto gap1 = [&](int g) { gap0(NM + g); };
+      mstep(a_s, 0, gap0);
+      mstep(a_s, 1, gap1);
       __syncthreads();
     }
   }
@@ -501,11 +508,13 @@ void x6_transpose(const float* src, int64_t ld_src, int64_t rows, int64_t cols, 
                      ld_dst, tc);
 }
 
-// GMR_GEMM_X6_PIPE = 1: the double-buffered kernels split the next tile between the MFMAs (A/B)
+// GMR_GEMM_X6_PIPE = 1 / 0 (read once): every call / no call takes the pipelined loop, whatever its plan or
+// GMR_GEMM_X6_PIPE1 flag says; = 2: the 256 x 128 and 128 x 256 tiles take it, the others follow their plan (the
+// one form that won standalone, for epoch A/B runs); unset (-1): the plan decides
 static int x6_pipe() {
   static const int v = [] {
     const char* e = getenv("GMR_GEMM_X6_PIPE");
-    return e ? atoi(e) : 0;
+    return e ? atoi(e) : -1;
   }();
   return v;
 }
@@ -541,7 +550,9 @@ int x6_inplace() {
 
 int x6_launch(int bm, int bn, dim3 grid, hipStream_t st, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
               const float* B, int64_t ldb, float* C, int64_t ldc, const Epi& epi, int tiles_n, int64_t kps, float* ws,
-              bool akc, bool bkc) {
+              bool akc, bool bkc, bool pipe) {
+  if (x6_pipe() == 0 || x6_pipe() == 1) pipe = x6_pipe() == 1;
+  if (x6_pipe() == 2) pipe = pipe || bm * bn == 256 * 128;
 #define GMR_X6(BM_, BN_, WGM_, WGN_, NBUF_, OCC_)                                                                \
   {                                                                                                                \
     if (!akc || !bkc) {                                                                                            \
@@ -555,7 +566,7 @@ int x6_launch(int bm, int bn, dim3 grid, hipStream_t st, int64_t M, int64_t N, i
         return -1;                                                                                                 \
       return 0;                                                                                                    \
     }                                                                                                              \
-    if (NBUF_ == 2 && x6_pipe())                                                                                   \
+    if (NBUF_ == 2 && pipe)                                                                                        \
       hipLaunchKernelGGL((gemm_x6_kernel<BM_, BN_, WGM_, WGN_, NBUF_, OCC_, NBUF_ - 1>), grid, dim3(64 * WGM_ * WGN_), \
                          0, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps, ws);                           \
     else                                                                                                           \
@@ -582,7 +593,7 @@ int x6_launch(int bm, int bn, dim3 grid, hipStream_t st, int64_t M, int64_t N, i
     // set (profiles/r02x6_study.txt); with the two sets of round 6 it spills 392 bytes per lane, so it is
     // opt-in, GMR_GEMM_X6_NB128 = 3.)
     const int nb = x6_nb128();
-    if (nb == 2) GMR_X6(128, 128, 2, 2, 2, 1)
+    if (nb == 2 || (pipe && akc && bkc && nb == 0)) GMR_X6(128, 128, 2, 2, 2, 1)  // the pipelined loop double-buffers
     if (nb == 3) GMR_X6(128, 128, 2, 2, 1, 3)
     GMR_X6(128, 128, 2, 2, 1, 2)
   }

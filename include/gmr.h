@@ -47,6 +47,9 @@ extern "C" {
 #define GMR_GEMM_MFMA32 (1 << 25)
 #define GMR_GEMM_X6 (1 << 26)        /* tile flag: split-bf16 operands on the bf16 MFMA (six products, fp32-accurate) */
 #define GMR_GEMM_F32 (1 << 27)       /* tile flag: force the fp32-input MFMA (overrides GMR_GEMM_X6=1 in the environment) */
+#define GMR_GEMM_X6_PIPE1 (1 << 28)  /* tile flag: a split-bf16 call on a >= 128^2 tile runs the pipelined k loop (the next
+                                        tile's split between this tile's MFMAs; 128^2: one double-buffered block per CU).
+                                        Same plan, same sums, bit for bit; no effect on any other call */
 #define GMR_EPI_DRELU 8        /* C = aux[m,n] > 0 ? alpha*acc : 0  ReLU (+ dropout) backward  */
 #define GMR_EPI_LEAKY_NORM 9   /* C = leaky_relu(alpha*acc + bias, slope) and its row normalisation in the split-K
                                   reduce: aux (WRITTEN, ld_aux) = C[m] / max(|C[m]|, 1e-12), rowvec1 (WRITTEN) = that
@@ -256,7 +259,9 @@ int gmr_topk_to_user_csr(int64_t n_users, int32_t k, const int32_t* topk, int64_
  * exactly into three bf16 terms and six products accumulated in fp32 (fp32-accurate: error vs fp64 within
  * the fp32-MFMA kernel's bound, tests/test_kernels_gpu.py); | GMR_GEMM_X6 forces it, | GMR_GEMM_F32 (or
  * any staging / MFMA-shape flag) keeps the fp32-input MFMA, and the environment variable GMR_GEMM_X6=0
- * turns it off for every call.  gmr_gemm_kernel_kind returns the matrix path a call with these
+ * turns it off for every call.  | GMR_GEMM_X6_PIPE1 picks the pipelined k loop of such a call (the environment
+ * variable GMR_GEMM_X6_PIPE = 1 / 0, read once, forces it on / off for every call, = 2 on for the 256 x 128
+ * tiles).  gmr_gemm_kernel_kind returns the matrix path a call with these
  * arguments takes: 6 (split-bf16), 32 (v_mfma_f32_32x32x2_f32) or 16 (v_mfma_f32_16x16x4_f32). */
 int32_t gmr_gemm_kernel_kind(int32_t trans_a, int32_t trans_b, int64_t M, int64_t N, int64_t K, int32_t tile,
                              int32_t split_k, int32_t aligned);
