@@ -269,6 +269,19 @@ SIGNATURES = {
                                  U64, P, P, I64, P, I64, P]),
     "gmr_smore_fuse_bwd": (I32, [I64, P, I64, P, P, I64, P, I64, P, I64, F32, P, P, P, P, P, P, P, I64, P, I64, P,
                                  I64, P, I64, P]),
+    "gmr_lgm_tile_rows": (I32, []),
+    "gmr_lgm_max_blocks": (I32, []),
+    "gmr_lgm_lat_ws_floats": (I64, [I64, I32]),
+    "gmr_lgm_hyper_fwd": (I32, [I64, I64, I32, P, I64, P, I64, P, P, P, P, I64, P, P, I64, F32, F32, I32, U64, U64, P,
+                                P, I64, I32, P]),
+    "gmr_lgm_draws": (I32, [I64, I32, I32, U64, U64, F32, P, P, P]),
+    "gmr_lgm_lat": (I32, [I64, P, I64, I32, P, P, I64, P, I64, I32, P, P]),
+    "gmr_lgm_apply": (I32, [I64, P, I64, I32, P, P, I64, I32, I32, P]),
+    "gmr_lgm_combine_fwd": (I32, [I64, P, I64, P, I64, P, I64, I32, P, F32, P, I64, P, P, P, I32, P]),
+    "gmr_lgm_combine_bwd": (I32, [I64, P, I64, P, I64, P, P, P, F32, P, I64, P, I32, P]),
+    "gmr_lgm_dh": (I32, [I64, P, P, I64, P, I32, P, I64, P, P, I64, F32, F32, P, I64, I32, P]),
+    "gmr_lgm_logit_bwd": (I32, [I64, I64, I32, P, I64, P, P, P, I64, P, I64, I32, P]),
+    "gmr_lgm_reg": (I32, [I32, I64, P, I64, P, P, P, F32, P, I64, P, P]),
 }
 
 _lib = None

@@ -9,7 +9,8 @@ import torch
 # model name -> module of this package (reference: importlib of models.<name.lower()>, utils.py:28-41)
 _MODELS = {"DiffMM": "diffmm", "DiffRec": "diffrec", "VBPR": "vbpr", "GenRecV1": "genrecv1",
            "FREEDOM": "freedom", "RFFREEDOM": "rffreedom", "LD4MRec": "ld4mrec", "DDRM": "ddrm", "BM3": "bm3",
-           "RFBM3": "rfbm3", "MGCN": "mgcn", "RFMGCN": "rfmgcn", "LATTICE": "lattice", "SMORE": "smore"}
+           "RFBM3": "rfbm3", "MGCN": "mgcn", "RFMGCN": "rfmgcn", "LATTICE": "lattice", "SMORE": "smore",
+           "LGMRec": "lgmrec"}
 
 
 def get_local_time():

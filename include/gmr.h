@@ -1127,6 +1127,59 @@ int gmr_smore_fuse_bwd(int64_t n, const float* dall, int64_t ldda, const float* 
                        const float* Wf, int64_t ldw, float* dabf, int64_t lddabf, float* dc, int64_t lddc, float* z,
                        int64_t ldz, void* stream);
 
+/* ---------------------------------------------------------------- LGMRec (models/lgmrec.py; csrc/lgmrec.hip)
+ * The global hypergraph embedding block, fp32, deterministic (no float atomics; no result depends on the grid).
+ * H = hyper_num, 1..64 (anything else is an argument error).  Tables S, h, d h, d L are n x 2H, [v | t]; lat and
+ * d lat are [2][H][64].  max_blocks caps a launch's grid (0: gmr_lgm_max_blocks()); every row kernel loops over its
+ * rows with that grid, and a row's result does not depend on it.
+ * hyper_fwd: the N = U + I rows, users first.  An item row i reads its logits Lv[i], Lt[i] (H columns of the
+ *   projection product, ldlv / ldlt); a user row sums its items' logit rows over the interaction CSR in column order.
+ *   S = softmax((L + g) / tau), h = keep S / p_keep.  gv, gt (N x H, ldg): given Gumbel draws, else drawn from Philox
+ *   keyed on (seed, site, step, row within users / items, column); site = 4 m + 2 (item row) + (dropout).  drop_mode
+ *   0: no dropout (also whenever p_keep = 1); 1: keepv, keept (N x H bytes, ldk) given; 2: drawn.
+ * draws: the draws of an even site as hyper_fwd makes them, g (n x H) and keep (n x H bytes) of site + 1; either NULL.
+ * lat: lat[m] = A[:, m H : m H + H]^T X_m over n rows (Xv, Xt: n x 64, ldx).  32-row tiles write partials to ws
+ *   (gmr_lgm_lat_ws_floats(n, H) floats); a second pass adds them in tile order (sixteen fp64 slices, one tree).
+ * apply: mode 0: Y (n x 128) = [A_v M_v | A_t M_t]; mode 1: Y (n x 64) += A_v M_v + A_t M_t.
+ * combine_fwd: x_m = h_m lat_m; all = cge + n(mge_v) + n(mge_t) + alpha n(x_v + x_t) with n(x) = x / max(|x|, 1e-12);
+ *   CLN (n x 128, packed) = [n(x_v) | n(x_t)], nrmCL [2][n] their clamped norms (the layout of
+ *   gmr_contrast_fused_nbwd_f32 and gmr_scatter_sorted_nbwd_f32), nrm3 [3][n] = |mge_v|, |mge_t|, |x_v + x_t| clamped.
+ * combine_bwd: from dall: dmge (n x 128) and dK (n x 128, packed) += [d | d], d = alpha nbwd(x_v + x_t)(dall).
+ * dh: out[r, m H + k] = <X_m[r], M[m][k]> (+ acc[r, m H + k]); with S and h given the result is taken through the
+ *   dropout and softmax backward: out = S (d S - <d S, S>) / tau, d S = d h / p_keep where h != 0, else 0 (finite
+ *   where a probability underflowed to 0).
+ * logit_bwd: outm[i, k] = dL[U + i, m H + k] + sum over the users u of item i (trp, tcol: the I x U transposed CSR,
+ *   users ascending) of dL[u, m H + k].
+ * reg: out[0] = coef (|all[users]|_F + |all[U + pos]|_F + |all[U + neg]|_F); contrib (3B x 64) += its rows. */
+int32_t gmr_lgm_tile_rows(void);
+int32_t gmr_lgm_max_blocks(void);
+int64_t gmr_lgm_lat_ws_floats(int64_t n, int32_t H);
+int gmr_lgm_hyper_fwd(int64_t U, int64_t I, int32_t H, const float* Lv, int64_t ldlv, const float* Lt, int64_t ldlt,
+                      const int32_t* rowptr, const int32_t* col, const float* gv, const float* gt, int64_t ldg,
+                      const uint8_t* keepv, const uint8_t* keept, int64_t ldk, float tau, float p_keep,
+                      int32_t drop_mode, uint64_t seed, uint64_t step, float* S, float* h, int64_t ldh,
+                      int32_t max_blocks, void* stream);
+int gmr_lgm_draws(int64_t n, int32_t H, int32_t site, uint64_t seed, uint64_t step, float p_keep, float* g,
+                  uint8_t* keep, void* stream);
+int gmr_lgm_lat(int64_t n, const float* A, int64_t lda, int32_t H, const float* Xv, const float* Xt, int64_t ldx,
+                float* ws, int64_t ws_floats, int32_t max_blocks, float* lat, void* stream);
+int gmr_lgm_apply(int64_t n, const float* A, int64_t lda, int32_t H, const float* M, float* Y, int64_t ldy,
+                  int32_t mode, int32_t max_blocks, void* stream);
+int gmr_lgm_combine_fwd(int64_t n, const float* cge, int64_t ldc, const float* mge, int64_t ldm, const float* h,
+                        int64_t ldh, int32_t H, const float* lat, float alpha, float* all, int64_t ldo, float* CLN,
+                        float* nrmCL, float* nrm3, int32_t max_blocks, void* stream);
+int gmr_lgm_combine_bwd(int64_t n, const float* dall, int64_t ldda, const float* mge, int64_t ldm, const float* CLN,
+                        const float* nrmCL, const float* nrm3, float alpha, float* dmge, int64_t lddm, float* dK,
+                        int32_t max_blocks, void* stream);
+int gmr_lgm_dh(int64_t n, const float* Xv, const float* Xt, int64_t ldx, const float* M, int32_t H, const float* acc,
+               int64_t ldacc, const float* S, const float* h, int64_t ldh, float p_keep, float tau, float* out,
+               int64_t ldo, int32_t max_blocks, void* stream);
+int gmr_lgm_logit_bwd(int64_t U, int64_t I, int32_t H, const float* dL, int64_t lddl, const int32_t* trp,
+                      const int32_t* tcol, float* outv, int64_t ldov, float* outt, int64_t ldot, int32_t max_blocks,
+                      void* stream);
+int gmr_lgm_reg(int32_t B, int64_t U, const float* all, int64_t lda, const int32_t* users, const int32_t* pos,
+                const int32_t* neg, float coef, float* contrib, int64_t ldc, float* out, void* stream);
+
 /* (Round 5's native executor of a captured HIP graph, gmr_graph_exec_*, was removed in round 6: its replayed
  * step ran slower on the GPU than eager issue; the host tape of gmr/tape.py removes the Python issue cost and
  * keeps the eager streams and order.) */
