@@ -614,7 +614,7 @@ Plan make_plan_core(int ta, int tb, int64_t M, int64_t N, int64_t K, int tile, i
   const bool x6_64 = x6 && ((tile & GMR_GEMM_X6) || default_x6_64());
   const bool x6_pipe1 = tile & GMR_GEMM_X6_PIPE1;
   tile &= ~(GMR_GEMM_MFMA16 | GMR_GEMM_MFMA32 | GMR_GEMM_GLDS | GMR_GEMM_REGSTAGE | GMR_GEMM_X6 | GMR_GEMM_F32 |
-            GMR_GEMM_X6_PIPE1);
+            GMR_GEMM_X6_PIPE1 | GMR_GEMM_X6_COPY);
   if (tile == 0) {
     // measured on MI355X (scripts/gemm_bench.py): 256^2 tiles win the long-K products of the
     // denoiser (M >= 2048, N >= 1000, K >= 4096; one 16-wave block per CU), 128^2 the wide
@@ -702,9 +702,9 @@ Plan make_plan_core(int ta, int tb, int64_t M, int64_t N, int64_t K, int tile, i
   return p;
 }
 
-// TN / NN / TT calls whose NT form takes the split-bf16 kernel copy their m- / n-contiguous operands
-// k-contiguous into the workspace (gemm_x6.hip x6_transpose: 2 x 4 bytes per element, a few percent of
-// the product's time at the denoiser shapes) and run as NT; otherwise the fp32-input MFMA plan
+// TN / NN / TT calls whose NT form takes the split-bf16 kernel run on that plan: xpose marks the m- / n-contiguous
+// operands, which gmr_gemm_f32 reads in place where it can (gemm_x6.hip TrTile) and otherwise copies k-contiguous
+// into the workspace (x6_transpose) - the workspace bound counts every copy; otherwise the fp32-input MFMA plan
 Plan make_plan(int ta, int tb, int64_t M, int64_t N, int64_t K, int tile, int split_k) {
   if (ta || !tb) {
     Plan q = make_plan_core(0, 1, M, N, K, tile, split_k, true);
@@ -780,7 +780,7 @@ extern "C" int gmr_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t M, int64_t
   GMR_ARG(epilogue != GMR_EPI_ROWSCALE_AUX || rowvec1, "epilogue needs rowvec1");
   {
     const int t = tile & ~(GMR_GEMM_MFMA16 | GMR_GEMM_MFMA32 | GMR_GEMM_GLDS | GMR_GEMM_REGSTAGE | GMR_GEMM_X6 |
-                           GMR_GEMM_F32 | GMR_GEMM_X6_PIPE1);
+                           GMR_GEMM_F32 | GMR_GEMM_X6_PIPE1 | GMR_GEMM_X6_COPY);
     GMR_ARG(t == 0 || t == 64 || t == 128 || t == 256 || t == 256128 || t == 128256 || t == 12864,
             "tile must be 0 (auto), 64, 128, 256, 256128, 128256 or 12864 (| GMR_GEMM_MFMA16 / GMR_GEMM_MFMA32)");
   }
@@ -802,11 +802,16 @@ extern "C" int gmr_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t M, int64_t
   // the split-bf16 kernel loads float4 granules: operands it reads in place must be 16-byte aligned
   if (pl.mf == 6 && !(((pl.xpose & 1) || a16) && ((pl.xpose & 2) || b16)))
     pl = make_plan_core(trans_a, trans_b, M, N, K, tile, split_k, false);
-  // GMR_X6_INPLACE = 1 / 2 (opt-in, gemm_x6.hip x6_inplace): TN / NN split-bf16 plans read their n- (and
-  // m-) contiguous operands in place (MnTile, single-float loads: any alignment) instead of copying them
-  // k-contiguous.  TT calls (A m-contiguous, B k-contiguous) always copy.
-  if ((pl.xpose & 2) && x6_inplace()) pl.xpose &= ~2;
-  if (pl.xpose == 1 && !trans_b && x6_inplace() == 2) pl.xpose = 0;
+  // TN / NN split-bf16 plans read an m- / n-contiguous operand in place (gemm_x6.hip TrTile: float4 granules along
+  // m / n, transposed LDS reads) when it is 16-byte aligned with a leading dimension that is a multiple of 4 and
+  // covers its rows rounded up to 4 (the last granule may straddle the end); otherwise that operand is copied
+  // k-contiguous, as every operand is with tile | GMR_GEMM_X6_COPY or GMR_X6_INPLACE = 0 (= 1: only B in place,
+  // = 2 / unset: both).  TT calls (A m-contiguous, B k-contiguous) always copy.
+  if (pl.mf == 6 && pl.xpose && !trans_b && !(tile & GMR_GEMM_X6_COPY) && x6_inplace() != 0) {
+    auto r4 = [](int64_t v) { return (v + 3) / 4 * 4; };
+    if (b16 && ldb >= r4(N)) pl.xpose &= ~2;
+    if ((pl.xpose & 1) && x6_inplace() != 1 && a16 && lda >= r4(M)) pl.xpose &= ~1;
+  }
   const WsLayout wl = ws_layout(pl, M, N, K);
   if (pl.xpose) {
     GMR_ARG(workspace && workspace_floats >= wl.total, "needs workspace of gmr_gemm_workspace_floats(...) floats");

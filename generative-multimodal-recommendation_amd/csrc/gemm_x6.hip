@@ -22,7 +22,7 @@ using namespace gmr_gemm;
 // 32x32x16 block: 2.7x the fp32 MFMA rate at the instruction level.
 // LDS: per stage and operand three planes [rows][32 k] of bf16 (64-byte rows); the 16-byte k
 // chunk c of row r sits at chunk c ^ ((r >> 2) & 3), so the 16 lanes of a fragment read hit 16
-// distinct bank groups.  Register staging (the split needs the values in VGPRs anyway); NBUF = 2
+// distinct bank groups (m- / n-contiguous operands read in place: [32 k][rows] planes, TrTile).  Register staging (the split needs the values in VGPRs anyway); NBUF = 2
 // double-buffers LDS (one barrier per k tile), NBUF = 1 for the 256^2 tile (2 barriers).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -133,48 +133,88 @@ struct KcTile {
 };
 
 // m- / n-contiguous operand tile (A stored K x M of a TN call, B stored K x N of an NN / TN call) read in place:
-// each thread owns one row of the tile and E = R x BK / NT consecutive k of it (8 or 16), loaded as single
-// floats (the 64 lanes of a load read 64 consecutive rows at one k: 256 contiguous bytes), so after the split
-// it writes 16-byte chunks of its own row: the same plane images as KcTile's, with no transposed copy in HBM,
-// and consecutive lanes write consecutive 64-byte rows (the 4-row quads of a float4 mapping all hit one half
-// of the banks and ran the TN gradients 8-10 % slower than copy + k-contiguous, profiles/r05zs_*).  Rows past
-// the operand's end load its last row (any alignment) and only reach C rows / columns the epilogue discards;
-// k past the slab's end is zeroed, never loaded.
+// float4 granules of 4 consecutive rows at one k (a wave loads whole 512-byte or 1-KiB row segments of the operand
+// as it lies), split per granule and stored as 8 bytes per plane into [k][row] planes: the transpose of KcTile's
+// image, the same bytes per plane.  mstep reads its fragments from them with ds_read_b64_tr_b16 (x6_tr_frag), which
+// hands each lane 4 consecutive k of its own row: two of them are the bf16x8 one ds_read_b128 takes from a [row][k]
+// image, so the MFMA inputs, and every output bit, are those of the k-contiguous path.
+// Swizzle: the 8-byte unit u = row / 4 of k row k sits at unit u ^ ((k & 3) << 3) of that row (R / 4 units, 256 or
+// 512 bytes).  A transposed read's 32-lane half takes 4 k rows x 8 units (2 x 16 rows); all k rows start on bank 0,
+// so unswizzled the 4 rows of a block collide 4-way; the XOR puts them in the 4 different 64-byte quarters of the
+// 256 bytes: 64 distinct banks.  The stores' 16-lane groups write 16 consecutive units of one k row, XOR-ed by one
+// constant: 32 distinct banks.
+// Rows: granules that start past the operand's last row are clamped onto its last in-bounds granule, and that one
+// may straddle the end (the caller guarantees ld >= rows rounded up to 4, a 16-byte aligned base and ld % 4 == 0):
+// such values only reach C rows / columns the epilogue discards.  k past the slab's end is zeroed, never loaded.
 template <int R, int NT>
-struct MnTile {
-  static constexpr int E = R * BK / NT;  // k per thread
-  static_assert(E % 8 == 0 && NT % R == 0, "whole 8-k chunks of one row per thread");
-  int off;  // element offset of (this thread's row, its first k) from the tile's (r0, k0)
-  int rr;   // the row within the tile
-  int kt;   // its first k
-  int64_t ld;
-  float v[E];
+struct TrTile {
+  static constexpr int N4 = R * BK / 4 / NT;
+  static constexpr int GR = R / 4;  // granules per k row
+  static_assert(N4 * NT * 4 == R * BK && NT % (4 * GR) == 0, "whole k rows per pass, k & 3 fixed per thread");
+  static_assert(R % 128 == 0, "the swizzle moves a unit by up to 24 within its k row, a 32-row block by up to 3");
+  int off[N4];
+  float4 r[N4];
 
-  __device__ __forceinline__ void init(int64_t r0, int64_t nrows, int64_t ld_) {
-    ld = ld_;
-    rr = threadIdx.x % R;
-    kt = (threadIdx.x / R) * E;
-    off = (int)(kt * ld + (min(r0 + rr, nrows - 1) - r0));
-  }
-  // base = element (row r0, k0); kleft = valid k of this tile (BK for a full one)
-  __device__ __forceinline__ void load(const float* __restrict__ base, int kleft) {
+  __device__ __forceinline__ void init(int64_t r0, int64_t nrows, int64_t ld) {
+    const int last = (int)(((nrows - 1) & ~(int64_t)3) - r0);  // first row of the last in-bounds granule
 #pragma unroll
-    for (int e = 0; e < E; ++e) v[e] = (kleft == BK || kt + e < kleft) ? base[off + e * ld] : 0.f;
+    for (int i = 0; i < N4; ++i) {
+      const int idx = threadIdx.x + NT * i;
+      const int kk = idx / GR, m4 = (idx % GR) * 4;
+      off[i] = (int)(kk * ld) + min(m4, last);
+    }
   }
-  // the three bf16 planes of one LDS stage (plane stride PL elements), KcTile / x6_store's image
+  // base = element (k0, row r0); kleft = valid k of this tile (BK for a full one)
+  __device__ __forceinline__ void load(const float* __restrict__ base, int kleft) {
+    if (kleft == BK) {
+#pragma unroll
+      for (int i = 0; i < N4; ++i) r[i] = *reinterpret_cast<const float4*>(base + off[i]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < N4; ++i) {
+        const int kk = (threadIdx.x + NT * i) / GR;
+        r[i] = kk < kleft ? *reinterpret_cast<const float4*>(base + off[i]) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+  }
+  // the three [k][row] bf16 planes of one LDS stage (plane stride R * BK elements)
   __device__ __forceinline__ void store(__bf16* s) const {
     constexpr int PL = R * BK;
 #pragma unroll
-    for (int c = 0; c < E / 8; ++c) {
-      bf16x8 h, m, l;
-      split3n<8>(v + 8 * c, h, m, l);
-      const int o = rr * BK + ((((kt >> 3) + c) ^ x6_swz(rr)) << 3);
-      *reinterpret_cast<bf16x8*>(s + o) = h;
-      *reinterpret_cast<bf16x8*>(s + PL + o) = m;
-      *reinterpret_cast<bf16x8*>(s + 2 * PL + o) = l;
+    for (int i = 0; i < N4; ++i) {
+      const int idx = threadIdx.x + NT * i;
+      const int kk = idx / GR, u = idx % GR;
+      const float v[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
+      bf16x4 h, m, l;
+      split3n<4>(v, h, m, l);
+      const int o = kk * R + ((u ^ ((kk & 3) << 3)) << 2);
+      *reinterpret_cast<bf16x4*>(s + o) = h;
+      *reinterpret_cast<bf16x4*>(s + PL + o) = m;
+      *reinterpret_cast<bf16x4*>(s + 2 * PL + o) = l;
     }
   }
 };
+
+// Per-lane element offset into a TrTile plane for the fragment of rows 32 J + l32 (J: the 32-row block of the tile):
+// within its 16-lane group, lane 4 q + p supplies the address of k row q, rows 4 p .. 4 p + 3 of the group's 16
+// (ds_read_b64_tr_b16's address map), the groups being (h, row half) = (0, 0), (0, 1), (1, 0), (1, 1) as the MFMA
+// operand wants them; k = 8 h + q here, x6_tr_frag adds 16 s (+ 4).
+template <int R>
+__device__ __forceinline__ int x6_tr_lane_off(int J) {
+  const int lane = threadIdx.x & 63;
+  const int q = (lane & 15) >> 2, p = lane & 3, gs = (lane >> 4) & 1, h = lane >> 5;
+  return (8 * h + q) * R + ((((J ^ q) << 3) + 4 * gs + p) << 2);  // unit (8 J + 4 gs + p) ^ (q << 3)
+}
+
+// the bf16x8 fragment (k = 16 s + 8 h + 0..7 of the lane's row) of one TrTile plane: two transposed reads, 4 k each.
+// EXEC must be all ones here (the gather crosses lanes): every caller is in wave-uniform control flow.
+template <int R>
+__device__ __forceinline__ bf16x8 x6_tr_frag(const __bf16* pl, int o, int s) {
+  typedef __attribute__((address_space(3))) bf16x4* lds4;
+  const bf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)(pl + o + 16 * s * R));
+  const bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)(pl + o + (16 * s + 4) * R));
+  return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+}
 
 // one k tile of a k-contiguous operand straight into ring registers d (KcTile's offsets; full tile or the
 // zero-padded last one): the loads of later ring slots stay in flight while earlier slots are split
@@ -246,6 +286,13 @@ __global__ void __launch_bounds__(64 * WGM * WGN, OCC) gemm_x6_kernel(int64_t M,
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = sml[i][j][e] = 0.f;
 
+  // m- / n-contiguous operands (TrTile planes): the lane's offsets for its row blocks' transposed reads
+  [[maybe_unused]] int tra[TM], trb[TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i) tra[i] = AKC ? 0 : x6_tr_lane_off<BM>(wm * (WTM / 32) + i);
+#pragma unroll
+  for (int j = 0; j < TN; ++j) trb[j] = BKC ? 0 : x6_tr_lane_off<BN>(wn * (WTN / 32) + j);
+
   // one 16-deep MFMA step s (k = 16 s + 8 h + j: chunk 2 s + h of the 32-deep rows) of a stage; gap(g) is called
   // after the step's g-th MFMA (the pipelined loop puts a piece of the next tile's split there)
   auto mstep = [&](const __bf16* a_s, int s, auto&& gap) {
@@ -253,19 +300,29 @@ __global__ void __launch_bounds__(64 * WGM * WGN, OCC) gemm_x6_kernel(int64_t M,
     bf16x8 fb[3][TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-      const int row = wn * WTN + j * 32 + l32;
-      const int off = row * BK + (((2 * s + h) ^ x6_swz(row)) << 3);
+      if constexpr (BKC) {
+        const int row = wn * WTN + j * 32 + l32;
+        const int off = row * BK + (((2 * s + h) ^ x6_swz(row)) << 3);
 #pragma unroll
-      for (int p = 0; p < 3; ++p) fb[p][j] = *reinterpret_cast<const bf16x8*>(b_s + p * BPL + off);
+        for (int p = 0; p < 3; ++p) fb[p][j] = *reinterpret_cast<const bf16x8*>(b_s + p * BPL + off);
+      } else {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) fb[p][j] = x6_tr_frag<BN>(b_s + p * BPL, trb[j], s);
+      }
     }
     // A fragments read per row block: 12 live registers, not 12 TM; the pipelined loop (one block per CU) reads
     // them all ahead of the step's first MFMA, since nothing moves across its gaps
     bf16x8 fa_[TM][3];
     auto read_a = [&](int i) {
-      const int row = wm * WTM + i * 32 + l32;
-      const int off = row * BK + (((2 * s + h) ^ x6_swz(row)) << 3);
+      if constexpr (AKC) {
+        const int row = wm * WTM + i * 32 + l32;
+        const int off = row * BK + (((2 * s + h) ^ x6_swz(row)) << 3);
 #pragma unroll
-      for (int p = 0; p < 3; ++p) fa_[i][p] = *reinterpret_cast<const bf16x8*>(a_s + p * APL + off);
+        for (int p = 0; p < 3; ++p) fa_[i][p] = *reinterpret_cast<const bf16x8*>(a_s + p * APL + off);
+      } else {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) fa_[i][p] = x6_tr_frag<BM>(a_s + p * APL, tra[i], s);
+      }
     };
     if constexpr (PIPE == 1) {
 #pragma unroll
@@ -297,8 +354,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN, OCC) gemm_x6_kernel(int64_t M,
 
   auto nogap = [](int) {};
   static_assert((AKC && BKC) || PIPE == 0, "m- / n-contiguous operands: the PIPE 0 loop only");
-  std::conditional_t<AKC, KcTile<BM, NT>, MnTile<BM, NT>> ra;
-  std::conditional_t<BKC, KcTile<BN, NT>, MnTile<BN, NT>> rb;
+  std::conditional_t<AKC, KcTile<BM, NT>, TrTile<BM, NT>> ra;
+  std::conditional_t<BKC, KcTile<BN, NT>, TrTile<BN, NT>> rb;
   ra.init(m0, M, lda);
   rb.init(n0, N, ldb);
   const float* a0 = AKC ? A + m0 * lda : A + m0;
@@ -323,7 +380,12 @@ __global__ void __launch_bounds__(64 * WGM * WGN, OCC) gemm_x6_kernel(int64_t M,
       } else {
         ra.load(a0 + k0 * lda, kleft);
       }
-      rb.load(b0 + k0 * ldb, kleft);
+      if constexpr (BKC) {
+        if (kleft == BK) rb.load(b0 + k0);
+        else rb.load_tail(b0 + k0, kleft);
+      } else {
+        rb.load(b0 + k0 * ldb, kleft);
+      }
     }
   };
   auto store = [&](__bf16* s) {  // the registers of one k tile -> the planes of one LDS stage
@@ -536,16 +598,37 @@ static int x6_nb128() {
   return v;
 }
 
-// GMR_X6_INPLACE = 0 (default): TN / NN split-bf16 calls copy their m- / n-contiguous operands k-contiguous
-// first; 1: B read in place (MnTile), A copied; 2: both read in place.  Opt-in: the in-place kernels ran the
-// denoiser gradient products 4-10 % slower than copy + k-contiguous kernel, epoch unchanged
-// (profiles/r05zt_x6_inplace_*.txt)
+// GMR_X6_INPLACE (read once; A/B runs): unset (-1): the plan's default (gemm.hip: eligible m- / n-contiguous operands
+// of TN / NN split-bf16 calls are read in place, TrTile); 0: always copy them k-contiguous first; 1: only B in place,
+// the m-contiguous A of TN calls copied; 2: both in place
 int x6_inplace() {
   static const int v = [] {
     const char* e = getenv("GMR_X6_INPLACE");
-    return e ? atoi(e) : 0;
+    return e ? atoi(e) : -1;
   }();
   return v;
+}
+
+// the plain loop on m- / n-contiguous operands read in place (TrTile: whole 128-row operand tiles only)
+template <int BM, int BN, int WGM, int WGN, int NBUF, int OCC>
+static int x6_launch_tr(bool akc, bool bkc, dim3 grid, hipStream_t st, int64_t M, int64_t N, int64_t K, const float* A,
+                        int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, const Epi& epi, int tiles_n,
+                        int64_t kps, float* ws) {
+  if constexpr (BM % 128 == 0 && BN % 128 == 0) {
+    const dim3 blk(64 * WGM * WGN);
+    if (akc)
+      hipLaunchKernelGGL((gemm_x6_kernel<BM, BN, WGM, WGN, NBUF, OCC, 0, true, false>), grid, blk, 0, st, M, N, K, A, lda,
+                         B, ldb, C, ldc, epi, tiles_n, kps, ws);
+    else if (!bkc)
+      hipLaunchKernelGGL((gemm_x6_kernel<BM, BN, WGM, WGN, NBUF, OCC, 0, false, false>), grid, blk, 0, st, M, N, K, A, lda,
+                         B, ldb, C, ldc, epi, tiles_n, kps, ws);
+    else
+      hipLaunchKernelGGL((gemm_x6_kernel<BM, BN, WGM, WGN, NBUF, OCC, 0, false, true>), grid, blk, 0, st, M, N, K, A, lda,
+                         B, ldb, C, ldc, epi, tiles_n, kps, ws);
+    return 0;
+  } else {
+    return -1;
+  }
 }
 
 int x6_launch(int bm, int bn, dim3 grid, hipStream_t st, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
@@ -555,17 +638,9 @@ int x6_launch(int bm, int bn, dim3 grid, hipStream_t st, int64_t M, int64_t N, i
   if (x6_pipe() == 2) pipe = pipe || bm * bn == 256 * 128;
 #define GMR_X6(BM_, BN_, WGM_, WGN_, NBUF_, OCC_)                                                                \
   {                                                                                                                \
-    if (!akc || !bkc) {                                                                                            \
-      if (akc)                                                                                                     \
-        hipLaunchKernelGGL((gemm_x6_kernel<BM_, BN_, WGM_, WGN_, NBUF_, OCC_, 0, true, false>), grid,              \
-                           dim3(64 * WGM_ * WGN_), 0, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps, ws); \
-      else if (!bkc)                                                                                               \
-        hipLaunchKernelGGL((gemm_x6_kernel<BM_, BN_, WGM_, WGN_, NBUF_, OCC_, 0, false, false>), grid,             \
-                           dim3(64 * WGM_ * WGN_), 0, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps, ws); \
-      else                                                                                                         \
-        return -1;                                                                                                 \
-      return 0;                                                                                                    \
-    }                                                                                                              \
+    if (!akc || !bkc)                                                                                              \
+      return x6_launch_tr<BM_, BN_, WGM_, WGN_, NBUF_, OCC_>(akc, bkc, grid, st, M, N, K, A, lda, B, ldb, C, ldc, epi, \
+                                                             tiles_n, kps, ws);                                   \
     if (NBUF_ == 2 && pipe)                                                                                        \
       hipLaunchKernelGGL((gemm_x6_kernel<BM_, BN_, WGM_, WGN_, NBUF_, OCC_, NBUF_ - 1>), grid, dim3(64 * WGM_ * WGN_), \
                          0, st, M, N, K, A, lda, B, ldb, C, ldc, epi, tiles_n, kps, ws);                           \

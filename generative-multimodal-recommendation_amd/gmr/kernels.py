@@ -216,7 +216,9 @@ def zero_(t):
 
 # ----------------------------------------------------------------------------- GEMM
 _gemm_kinds = {}
-# tile flags OR-ed into every gemm() call (tests: GMR_GEMM_F32 = 1 << 27 runs a whole path on the fp32-input MFMA)
+# tile flags OR-ed into every gemm() call (tests: GMR_GEMM_F32 = 1 << 27 runs a whole path on the fp32-input MFMA;
+# GMR_GEMM_X6_COPY = 1 << 29 makes TN / NN split-bf16 calls copy their operands k-contiguous, not read them in place)
+GEMM_X6_COPY = 1 << 29
 GEMM_TILE_FLAGS = 0
 
 

@@ -50,6 +50,8 @@ extern "C" {
 #define GMR_GEMM_X6_PIPE1 (1 << 28)  /* tile flag: a split-bf16 call on a >= 128^2 tile runs the pipelined k loop (the next
                                         tile's split between this tile's MFMAs; 128^2: one double-buffered block per CU).
                                         Same plan, same sums, bit for bit; no effect on any other call */
+#define GMR_GEMM_X6_COPY (1 << 29)   /* tile flag: a TN / NN split-bf16 call copies its m- / n-contiguous operands k-contiguous
+                                        into the workspace instead of reading them in place.  Same sums, bit for bit */
 #define GMR_EPI_DRELU 8        /* C = aux[m,n] > 0 ? alpha*acc : 0  ReLU (+ dropout) backward  */
 #define GMR_EPI_LEAKY_NORM 9   /* C = leaky_relu(alpha*acc + bias, slope) and its row normalisation in the split-K
                                   reduce: aux (WRITTEN, ld_aux) = C[m] / max(|C[m]|, 1e-12), rowvec1 (WRITTEN) = that
@@ -261,7 +263,11 @@ int gmr_topk_to_user_csr(int64_t n_users, int32_t k, const int32_t* topk, int64_
  * any staging / MFMA-shape flag) keeps the fp32-input MFMA, and the environment variable GMR_GEMM_X6=0
  * turns it off for every call.  | GMR_GEMM_X6_PIPE1 picks the pipelined k loop of such a call (the environment
  * variable GMR_GEMM_X6_PIPE = 1 / 0, read once, forces it on / off for every call, = 2 on for the 256 x 128
- * tiles).  gmr_gemm_kernel_kind returns the matrix path a call with these
+ * tiles).  TN / NN calls whose NT form qualifies run on it as well: an m- / n-contiguous operand that is 16-byte
+ * aligned, with a leading dimension that is a multiple of 4 and >= its rows rounded up to 4 (up to 3 floats past
+ * the last row of each k line are read, never used), is read in place; any other, and every one under
+ * | GMR_GEMM_X6_COPY or GMR_X6_INPLACE=0, is first copied k-contiguous into the workspace (same sums, bit for
+ * bit; gmr_gemm_workspace_floats counts the copies either way).  gmr_gemm_kernel_kind returns the matrix path a call with these
  * arguments takes: 6 (split-bf16), 32 (v_mfma_f32_32x32x2_f32) or 16 (v_mfma_f32_16x16x4_f32). */
 int32_t gmr_gemm_kernel_kind(int32_t trans_a, int32_t trans_b, int64_t M, int64_t N, int64_t K, int32_t tile,
                              int32_t split_k, int32_t aligned);

@@ -15,6 +15,7 @@ from gmr import kernels as K  # noqa: E402
 
 MF_FLAG = {32: 1 << 25, 16: 1 << 24, 6: 1 << 26}  # GMR_GEMM_MFMA32 / MFMA16 / X6 (split bf16) (include/gmr.h)
 MF_FLAG[61] = MF_FLAG[6] | 1 << 28  # X6 | GMR_GEMM_X6_PIPE1: the split-bf16 kernel's pipelined k loop
+MF_FLAG[62] = MF_FLAG[6] | 1 << 29  # X6 | GMR_GEMM_X6_COPY: TN / NN operands copied k-contiguous, not read in place
 
 # name, M, N, K, trans_a, trans_b, calls per epoch
 SHAPES = [
@@ -72,7 +73,7 @@ def run(args):
         best = None
         for tile0 in args.tiles:
           for mf in args.mfma:
-           tile = tile0 | (MF_FLAG[mf] if (tile0 or mf in (6, 61)) else 0)
+           tile = tile0 | (MF_FLAG[mf] if (tile0 or mf in (6, 61, 62)) else 0)
            if args.acc and not kw:
                K.gemm(A, B, C, trans_a=bool(ta), trans_b=bool(tb), tile=tile)
                a64 = (A.t() if ta else A).double()
@@ -84,13 +85,23 @@ def run(args):
            for split in args.splits:
             for _ in range(3):
                 K.gemm(A, B, C, trans_a=bool(ta), trans_b=bool(tb), tile=tile, split_k=split, **kw)
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(args.reps):
-                K.gemm(A, B, C, trans_a=bool(ta), trans_b=bool(tb), tile=tile, split_k=split, **kw)
-            e.record()
-            torch.cuda.synchronize()
-            us = 1e3 * s.elapsed_time(e) / args.reps
+            if args.median:  # every launch (the copies of a call included) between its own pair of events
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                      for _ in range(args.reps)]
+                for s, e in ev:
+                    s.record()
+                    K.gemm(A, B, C, trans_a=bool(ta), trans_b=bool(tb), tile=tile, split_k=split, **kw)
+                    e.record()
+                torch.cuda.synchronize()
+                us = 1e3 * sorted(s.elapsed_time(e) for s, e in ev)[args.reps // 2]
+            else:
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                for _ in range(args.reps):
+                    K.gemm(A, B, C, trans_a=bool(ta), trans_b=bool(tb), tile=tile, split_k=split, **kw)
+                e.record()
+                torch.cuda.synchronize()
+                us = 1e3 * s.elapsed_time(e) / args.reps
             tf = 2.0 * M * N * Kd / (us * 1e-6) / 1e12
             print(f"{name:26s} {tile0:7d} m{mf} s{split:<2d} {us:9.1f} {tf:7.1f} {us * calls / 1e3:9.2f}", flush=True)
             best = us if best is None else min(best, us)
@@ -104,7 +115,8 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--splits", default="0")
     ap.add_argument("--only", default="", help="substring filter on shape names")
-    ap.add_argument("--mfma", default="32", help="MFMA shapes to try: 32 (32x32x2), 16 (16x16x4), 6 (split-bf16), 61 (split-bf16, pipelined k loop)")
+    ap.add_argument("--mfma", default="32", help="MFMA shapes to try: 32 (32x32x2), 16 (16x16x4), 6 (split-bf16), 61 (split-bf16, pipelined k loop), 62 (split-bf16, TN / NN operands copied)")
+    ap.add_argument("--median", action="store_true", help="time every launch by itself and print the median")
     ap.add_argument("--acc", action="store_true", help="also print the error vs an fp64 product")
     a = ap.parse_args()
     a.tiles = [int(t) for t in a.tiles.split(",")]
