@@ -1,9 +1,9 @@
 // Rectified-flow embedding generator (models/rf_modules.py of the reference: SimpleVelocityNet,
-// RFEmbeddingGenerator) for embedding_dim 64, hidden_dim 128.
+// RFEmbeddingGenerator) for embedding_dim 64, hidden_dim 128, condition_dim 64, 128 or 192.
 //
 //   gmr_rf_sample                    the whole Euler integration of generate() in one launch: a workgroup owns
 //                                    32 rows, activations stay in LDS, weights are read through L2, products on
-//                                    v_mfma_f32_32x32x2_f32
+//                                    v_mfma_f32_32x32x2_f32; the condition product in K chunks of at most 128 columns
 //   gmr_rf_act_fwd / gmr_rf_act_bwd  [LayerNorm] + SiLU [+ dropout mask] [+ residual] rows of the training step,
 //                                    LN weight / bias gradients as fixed-order column reductions (no float atomics)
 //   gmr_rf_time_embed, gmr_rf_interp, gmr_rf_head_fwd / _prior_fwd / _bwd, gmr_rf_losses
@@ -51,11 +51,13 @@ __device__ __forceinline__ float silu(float x) { return x / (1.f + expf(-x)); }
 // acc (32 rows x 32 columns col0..) += src[32][K] (LDS, row stride ld) . W[col][K]^T (global, k contiguous).  Lane l
 // feeds row / column l & 31 and the k half l >> 5: step s of the half multiplies k = (K / 2) (l >> 5) + s, so both
 // operands are float4 reads; every row's sum has one fixed order, whatever tile the row falls in.
+// tile_mm_ld: the same over the K columns of a wider weight that start at W (row stride ldw >= K floats, ldw % 4 == 0),
+// one K chunk of a product whose operand does not fit the LDS tile at once.
 template <int K>
-__device__ __forceinline__ void tile_mm(const float* __restrict__ src, int ld, const float* __restrict__ W, int col0,
-                                        floatx16& acc) {
+__device__ __forceinline__ void tile_mm_ld(const float* __restrict__ src, int ld, const float* __restrict__ W, int ldw,
+                                           int col0, floatx16& acc) {
   const int lane = threadIdx.x & 63, h = lane >> 5, r = lane & 31;
-  const float* wp = W + (size_t)(col0 + r) * K + h * (K / 2);
+  const float* wp = W + (size_t)(col0 + r) * ldw + h * (K / 2);
   const float* sp = src + r * ld + h * (K / 2);
 #pragma unroll 4
   for (int s = 0; s < K / 2; s += 4) {
@@ -66,6 +68,12 @@ __device__ __forceinline__ void tile_mm(const float* __restrict__ src, int ld, c
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
   }
+}
+
+template <int K>
+__device__ __forceinline__ void tile_mm(const float* __restrict__ src, int ld, const float* __restrict__ W, int col0,
+                                        floatx16& acc) {
+  tile_mm_ld<K>(src, ld, W, K, col0, acc);
 }
 
 __device__ __forceinline__ floatx16 zero16() {
@@ -108,6 +116,23 @@ __device__ __forceinline__ void tile_ln_silu(const float* buf, const float* __re
   __syncthreads();
 }
 
+// One K chunk of the condition encoder: columns [K0, K0 + CK) of the tile's condition rows into sT (tail rows: zeros,
+// never stored), then acc += sT . W[:, K0 .. K0 + CK)^T with W at row stride C.  Before a later chunk is staged, a
+// barrier: every wave has read the one before.  The barrier after staging also covers the z0 tile on the first call.
+template <int K0, int CK, int C>
+__device__ __forceinline__ void cond_chunk(int64_t N, int64_t r0, const float* __restrict__ cond, int64_t ldc,
+                                           float* sT, const float* __restrict__ W, floatx16& acc) {
+  static_assert(CK <= H && CK % 8 == 0 && K0 % 4 == 0 && K0 + CK <= C, "a chunk fits the LDS tile; float4 reads");
+  const int tid = threadIdx.x;
+  if (K0 > 0) __syncthreads();
+  for (int idx = tid; idx < TR * CK; idx += 256) {
+    const int r = idx / CK, c = idx % CK;
+    sT[r * LDH + c] = r0 + r < N ? cond[(r0 + r) * ldc + K0 + c] : 0.f;
+  }
+  __syncthreads();
+  tile_mm_ld<CK>(sT, LDH, W + K0, C, (tid >> 6) * 32, acc);
+}
+
 template <int C>
 __global__ __launch_bounds__(256) void rf_sample_kernel(int64_t N, const float* __restrict__ z0, int64_t ldz,
                                                         const float* __restrict__ cond, int64_t ldc,
@@ -120,18 +145,16 @@ __global__ __launch_bounds__(256) void rf_sample_kernel(int64_t N, const float* 
   __shared__ float sE[H], sS[64];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int64_t r0 = (int64_t)blockIdx.x * TR;
-  for (int idx = tid; idx < TR * C; idx += 256) {
-    const int r = idx / C, c = idx % C;
-    sT[r * LDH + c] = r0 + r < N ? cond[(r0 + r) * ldc + c] : 0.f;  // tail rows: zeros, never stored
-  }
   for (int idx = tid; idx < TR * D; idx += 256) {
     const int r = idx / D, c = idx % D;
     sZ[r * LDZ + c] = r0 + r < N ? z0[(r0 + r) * ldz + c] : 0.f;
   }
-  __syncthreads();
-  // condition encoder, once per tile
+  // condition encoder, once per tile.  sT holds at most H condition columns, so the product runs in K chunks of
+  // H (then the rest) into one accumulator: columns [0, 128) and [128, 192) at C = 192.  One chunk at C <= 128.
   floatx16 acc = zero16();
-  tile_mm<C>(sT, LDH, P + o.cw, w * 32, acc);
+  constexpr int C0 = C < H ? C : H;
+  cond_chunk<0, C0, C>(N, r0, cond, ldc, sT, P + o.cw, acc);
+  if constexpr (C > H) cond_chunk<H, C - H, C>(N, r0, cond, ldc, sT, P + o.cw, acc);
   tile_store(sC, w * 32, acc, P + o.cb);
   __syncthreads();
   tile_ln_silu(sC, P + o.cg, P + o.cbe, nullptr, nullptr, nullptr, sC);
@@ -523,7 +546,7 @@ __global__ void rf_rand_kernel(int64_t n, uint64_t seed, uint64_t step, float* _
 extern "C" int32_t gmr_rf_tile_rows(void) { return TR; }
 
 extern "C" int64_t gmr_rf_param_floats(int32_t C, int32_t L) {
-  if ((C != 64 && C != 128) || L < 1 || L > MAX_L) return -1;
+  if ((C != 64 && C != 128 && C != 192) || L < 1 || L > MAX_L) return -1;
   return rf_offsets(C, L).total;
 }
 
@@ -531,7 +554,7 @@ extern "C" int gmr_rf_sample(int64_t N, int32_t hidden, int32_t C, int32_t L, in
                              int64_t ldz, const float* cond, int64_t ldc, const float* params, float* out, int64_t ldo,
                              void* stream) {
   GMR_ARG(hidden == H, "rf_hidden_dim must be 128");
-  GMR_ARG(C == 64 || C == 128, "condition_dim must be 64 or 128");
+  GMR_ARG(C == 64 || C == 128 || C == 192, "condition_dim must be 64, 128 or 192");
   GMR_ARG(L >= 1 && L <= MAX_L, "rf_n_layers must be in 1..4");
   GMR_ARG(N >= 1 && N <= ((int64_t)1 << 31) * TR - TR && n_steps >= 1, "N >= 1 and n_steps >= 1");
   GMR_ARG(z0 && cond && params && out && ldz >= D && ldc >= C && ldo >= D, "bad pointers or strides");
@@ -542,8 +565,11 @@ extern "C" int gmr_rf_sample(int64_t N, int32_t hidden, int32_t C, int32_t L, in
   if (C == 64)
     hipLaunchKernelGGL(rf_sample_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, N, z0, ldz, cond, ldc, params, o,
                        L, n_steps, dt, out, ldo);
-  else
+  else if (C == 128)
     hipLaunchKernelGGL(rf_sample_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, N, z0, ldz, cond, ldc, params,
+                       o, L, n_steps, dt, out, ldo);
+  else
+    hipLaunchKernelGGL(rf_sample_kernel<192>, grid, dim3(256), 0, (hipStream_t)stream, N, z0, ldz, cond, ldc, params,
                        o, L, n_steps, dt, out, ldo);
   GMR_LAUNCHED();
   return GMR_OK;

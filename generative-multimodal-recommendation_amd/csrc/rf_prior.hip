@@ -1,4 +1,4 @@
-// The centred priors of the rectified-flow step, prior[r] = Z[r] - mean_seg(r)(Z), for the two backbones that pass one:
+// The centred priors of the rectified-flow step, prior[r] = Z[r] - mean_seg(r)(Z), for the backbones that pass one:
 //
 //   gmr_rf_item_inputs   RFBM3 (models/rfbm3.py:107-175 of the reference), from BM3's projected item tables T =
 //                        text_trs(text), V = image_trs(image) (I x 64 each, either may be absent): Z = V + T, the mean
@@ -10,6 +10,11 @@
 //                        (N x 64 each, N = U + I; in the model both are column blocks of the one table ab): Z =
 //                        0.5 (a + b); the mean is over the U user rows for r < U and over the I item rows otherwise.
 //                        MGCN carries both views to the users over R, so the user half has a mean of its own.
+//   gmr_rf_view3_inputs  RFSMORE (models/rfsmore.py:165-195), from SMORE's three views a, b, f and the fusion
+//                        preference gate g of the step (with that step's dropout mask and scale; N x 64 each, every
+//                        one with a row stride of its own: column blocks of abf and of saved in the model): Z =
+//                        (a + b + g f) / 3, the two segment means as for RFMGCN.  Writes the N x 64 prior and, on the
+//                        way, the N x 192 condition table [a | b | g f].
 //
 // Three small kernels behind either entry point, each a template over the functor that forms Z for a row: per-block
 // column sums of Z, the sum of a segment's block partials in one fixed order (one workgroup per segment), Z - mean.
@@ -61,6 +66,35 @@ struct ViewZ {
   int64_t ldb;
   __device__ __forceinline__ float4 operator()(int64_t row, int c) const {
     return gmr::f4_scale(0.5f, gmr::f4_add(ld4(a + row * lda + c), ld4(b + row * ldb + c)));
+  }
+};
+
+// Z = (a + b + g f) / 3; STORE: the condition row [a | b | g f] written on the way.  g f is one rounded product in
+// both passes (no contraction with the sum), so the condition's third block and the prior see the same number.
+template <bool STORE>
+struct View3Z {
+  const float* __restrict__ a;
+  int64_t lda;
+  const float* __restrict__ b;
+  int64_t ldb;
+  const float* __restrict__ f;
+  int64_t ldf;
+  const float* __restrict__ g;
+  int64_t ldg;
+  float* __restrict__ cond;
+  int64_t ldc;
+  __device__ __forceinline__ float4 operator()(int64_t row, int c) const {
+#pragma clang fp contract(off)
+    const float4 av = ld4(a + row * lda + c), bv = ld4(b + row * ldb + c);
+    const float4 fv = ld4(f + row * ldf + c), gv = ld4(g + row * ldg + c);
+    const float4 gf = make_float4(gv.x * fv.x, gv.y * fv.y, gv.z * fv.z, gv.w * fv.w);
+    if (STORE) {
+      st4(cond + row * ldc + c, av);
+      st4(cond + row * ldc + D + c, bv);
+      st4(cond + row * ldc + 2 * D + c, gf);
+    }
+    const float4 s = gmr::f4_add(gmr::f4_add(av, bv), gf);
+    return make_float4(s.x / 3.f, s.y / 3.f, s.z / 3.f, s.w / 3.f);
   }
 };
 
@@ -193,6 +227,32 @@ extern "C" int gmr_rf_view_prior(int64_t U, int64_t I, const float* a, int64_t l
   GMR_LAUNCHED();
   hipLaunchKernelGGL(rf_prior_sub_kernel, dim3(nbu + nbi), dim3(256), 0, (hipStream_t)stream, nbu, U, U + I, z, mean,
                      prior, ldp);
+  GMR_LAUNCHED();
+  return GMR_OK;
+}
+
+extern "C" int64_t gmr_rf_view3_inputs_ws_floats(int64_t U, int64_t I) { return gmr_rf_view_prior_ws_floats(U, I); }
+
+extern "C" int gmr_rf_view3_inputs(int64_t U, int64_t I, const float* a, int64_t lda, const float* b, int64_t ldb,
+                                   const float* f, int64_t ldf, const float* g, int64_t ldg, float* cond, int64_t ldc,
+                                   float* prior, int64_t ldp, float* ws, void* stream) {
+  GMR_ARG(U >= 1 && I >= 1 && U <= MAX_ROWS && I <= MAX_ROWS, "1 <= U, I <= 2^31 - 128 (a mean over no rows is NaN)");
+  GMR_ARG(a && b && f && g && cond && prior && ws && lda >= D && ldb >= D && ldf >= D && ldg >= D && ldc >= 3 * D &&
+              ldp >= D,
+          "bad pointers or strides");
+  GMR_ARG(aligned16(a) && aligned16(b) && aligned16(f) && aligned16(g) && aligned16(cond) && aligned16(prior) &&
+              aligned16(ws) && lda % 4 == 0 && ldb % 4 == 0 && ldf % 4 == 0 && ldg % 4 == 0 && ldc % 4 == 0 &&
+              ldp % 4 == 0,
+          "rows must be 16-byte aligned");
+  const int nbu = gmr::grid_for(U, RB), nbi = gmr::grid_for(I, RB);
+  float* mean = ws + (int64_t)(nbu + nbi) * D;  // [users | items]
+  hipLaunchKernelGGL(rf_prior_sum_kernel, dim3(nbu + nbi), dim3(256), 0, (hipStream_t)stream, nbu, U, U + I,
+                     View3Z<true>{a, lda, b, ldb, f, ldf, g, ldg, cond, ldc}, ws);
+  GMR_LAUNCHED();
+  hipLaunchKernelGGL(rf_prior_mean_kernel<16>, dim3(2), dim3(16 * D), 0, (hipStream_t)stream, nbu, nbi, U, I, ws, mean);
+  GMR_LAUNCHED();
+  hipLaunchKernelGGL(rf_prior_sub_kernel, dim3(nbu + nbi), dim3(256), 0, (hipStream_t)stream, nbu, U, U + I,
+                     View3Z<false>{a, lda, b, ldb, f, ldf, g, ldg, nullptr, 0}, mean, prior, ldp);
   GMR_LAUNCHED();
   return GMR_OK;
 }

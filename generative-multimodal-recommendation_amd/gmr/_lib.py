@@ -206,6 +206,8 @@ SIGNATURES = {
     "gmr_rf_item_inputs": (I32, [I64, I64, P, I64, P, I64, P, I64, P, I64, P, P]),
     "gmr_rf_view_prior_ws_floats": (I64, [I64, I64]),
     "gmr_rf_view_prior": (I32, [I64, I64, P, I64, P, I64, P, I64, P, P]),
+    "gmr_rf_view3_inputs_ws_floats": (I64, [I64, I64]),
+    "gmr_rf_view3_inputs": (I32, [I64, I64, P, I64, P, I64, P, I64, P, I64, P, I64, P, I64, P, P]),
     "gmr_rf_losses": (I32, [I64, P, I64, P, F32, P, P]),
     "gmr_rf_infonce_sampled_fwd_bwd": (I32, [I32, I64, P, I64, P, I64, I64, P, I32, P, U64, U64, U64, F32, F32, P, P,
                                              I64, P]),

@@ -2,7 +2,7 @@
 SimpleVelocityNet), backbone-agnostic: a backbone hands it the detached target table X1 ((U + I) x 64) and the
 condition table ((U + I) x C) and mixes generate()'s output into its evaluation embeddings.
 
-Supported: embedding_dim 64, rf_hidden_dim 128, rf_n_layers 1..4, C in {64, 128}, 1-RF (use_2rf False).
+Supported: embedding_dim 64, rf_hidden_dim 128, rf_n_layers 1..4, C in {64, 128, 192}, 1-RF (use_2rf False).
 
   train_step   X0 ~ N(0, 1), t ~ U[0, 1), X_t; the velocity net forward with saved pre-activations (the Linear
                layers on the GEMM with the BIAS epilogue, gmr_rf_act_fwd rows between them); the guidance / MSE head
@@ -78,7 +78,7 @@ class RFGenerator(nn.Module):
         super().__init__()
         C, L = int(condition_dim), int(n_layers)
         if int(_lib.load().gmr_rf_param_floats(C, L)) < 0:
-            raise NotImplementedError(f"condition_dim {C} / rf_n_layers {L}: the kernels take 64 or 128 and 1..4")
+            raise NotImplementedError(f"condition_dim {C} / rf_n_layers {L}: the kernels take 64, 128 or 192 and 1..4")
         self.U, self.I, self.N, self.C, self.L = int(n_users), int(n_items), int(n_users + n_items), C, L
         self.dev = device
         self.dropout, self.lr, self.wd = float(dropout), float(learning_rate), float(weight_decay)
@@ -348,7 +348,8 @@ class RFBackbone:
     """What the RF-on-X models share, mixed in before the backbone: class RFX(RFBackbone, X).  use_rf: False is X and
     allocates no generator.  The model adds its buffers in __init__ (when use_rf), rf_step_inputs() -> (X1, cond,
     prior or None), the tables of the last backbone step the RF step trains on, and forward_embeddings(z0=None), its
-    rule for mixing generate()'s rows into the evaluation tables once rf_warm()."""
+    rule for mixing generate()'s rows into the evaluation tables once rf_warm().  rf_condition_dim() is the width of
+    cond: 64 per modality unless the model says otherwise."""
 
     def __init__(self, config, dataloader):
         super().__init__(config, dataloader)
@@ -357,10 +358,14 @@ class RFBackbone:
         if not self.use_rf:
             return
         check_config(config)
-        self.rf_generator = RFGenerator(self.n_users, self.n_items, 64 * len(self.mods), self.device,
+        self.rf_generator = RFGenerator(self.n_users, self.n_items, self.rf_condition_dim(), self.device,
                                         seed=config_seed(config),
                                         **{kw: _get(config, key, d) for kw, (key, d) in RF_CONFIG.items()})
         self._training_epoch = -1  # incremented to 0 by the first pre_epoch_processing
+
+    def rf_condition_dim(self):
+        """Columns of the condition table: one 64-wide block per modality."""
+        return 64 * len(self.mods)
 
     # ------------------------------------------------------------------ state
     def extra_state(self):

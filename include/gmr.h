@@ -785,7 +785,7 @@ int gmr_frd_mean_fwd(int64_t n_rows, int64_t n_users, int32_t n_layers, const fl
                      const int64_t* ld_layers, const float* h, int64_t ldh, float* out, int64_t ldo, void* stream);
 
 /* ---------------------------------------------------------------- rectified-flow generator (models/rf_modules.py)
- * SimpleVelocityNet with embedding_dim 64 and hidden_dim 128, condition_dim C in {64, 128}, L = rf_n_layers in 1..4.
+ * SimpleVelocityNet with embedding_dim 64 and hidden_dim 128, condition_dim C in {64, 128, 192}, L = rf_n_layers in 1..4.
  * params: the net's named_parameters() order, every tensor dense and row-major (gmr_rf_param_floats(C, L) floats,
  * 16-byte aligned): time_embed.1 {W 128x64, b}; condition_encoder {W 128xC, b, LN w, LN b}; input_proj {W 128x64, b,
  * LN w, LN b}; L x res_blocks {W, b, LN w, LN b, W, b, LN w, LN b}; output_proj {W 128x128, b, LN w, LN b, W 64x128,
@@ -794,7 +794,8 @@ int64_t gmr_rf_param_floats(int32_t C, int32_t L); /* -1 outside the supported r
 int32_t gmr_rf_tile_rows(void);                    /* rows a workgroup of gmr_rf_sample owns */
 /* generate() (:896-975): z <- z + net(z, i / n_steps, cond) / n_steps for i = 0 .. n_steps - 1 from z0, dropout and
  * guidance off, the whole loop in one launch.  z0 N x 64 (ldz), cond N x C (ldc), out N x 64 (ldo); any N >= 1 (tail
- * rows are masked).  A row's result does not depend on N or on the rows around it.  hidden != 128, C or L outside
+ * rows are masked).  A row's result does not depend on N or on the rows around it.  The condition product runs in K
+ * chunks of at most 128 columns into one accumulator (two chunks at C = 192), in one fixed order per row.  hidden != 128, C or L outside
  * the range: GMR_ERR_ARG. */
 int gmr_rf_sample(int64_t N, int32_t hidden, int32_t C, int32_t L, int32_t n_steps, const float* z0, int64_t ldz,
                   const float* cond, int64_t ldc, const float* params, float* out, int64_t ldo, void* stream);
@@ -850,6 +851,17 @@ int gmr_rf_item_inputs(int64_t I, int64_t U, const float* T, int64_t ldt, const 
 int64_t gmr_rf_view_prior_ws_floats(int64_t U, int64_t I);
 int gmr_rf_view_prior(int64_t U, int64_t I, const float* a, int64_t lda, const float* b, int64_t ldb, float* prior,
                       int64_t ldp, float* ws, void* stream);
+/* RFSMORE's RF inputs (models/rfsmore.py:165-195) from SMORE's three views a, b, f and the fusion preference gate g
+ * of the step, dropout mask and scale included ((U + I) x 64 each, every one with a stride of its own: column blocks
+ * of a 192-wide and a 448-wide table in the model): cond ((U + I) x 192, ldc) = [a | b | g f], the first two blocks
+ * copies and the third the rounded fp32 product; prior ((U + I) x 64, ldp) = Z - mean_seg(Z), Z = (a + b + g f) / 3
+ * with that same product, the segments, the grid and the fixed-order means as gmr_rf_view_prior.  Nothing outside
+ * the two blocks is written.  1 <= U, I <= 2^31 - 128 (GMR_ERR_ARG otherwise; _ws_floats returns -1).  ws:
+ * gmr_rf_view3_inputs_ws_floats(U, I) floats.  All pointers 16-byte aligned, strides multiples of 4 floats. */
+int64_t gmr_rf_view3_inputs_ws_floats(int64_t U, int64_t I);
+int gmr_rf_view3_inputs(int64_t U, int64_t I, const float* a, int64_t lda, const float* b, int64_t ldb, const float* f,
+                        int64_t ldf, const float* g, int64_t ldg, float* cond, int64_t ldc, float* prior, int64_t ldp,
+                        float* ws, void* stream);
 /* out3 = [rf_loss = sum(row_parts) / (64 N), cl_loss = sum(cl_parts[0 : 2B]) / B, rf_loss + weight cl_loss] */
 int gmr_rf_losses(int64_t N, const double* row_parts, int64_t B, const double* cl_parts, float weight, float* out3,
                   void* stream);
