@@ -4,6 +4,8 @@
 //   gmr_rf_sample                    the whole Euler integration of generate() in one launch: a workgroup owns
 //                                    32 rows, activations stay in LDS, weights are read through L2, products on
 //                                    v_mfma_f32_32x32x2_f32; the condition product in K chunks of at most 128 columns
+//   gmr_rf_sample_mix                the same launch with the evaluation's mix as its epilogue: the final store of a
+//                                    tile writes base + ratio z (ratio a device scalar) instead of z
 //   gmr_rf_act_fwd / gmr_rf_act_bwd  [LayerNorm] + SiLU [+ dropout mask] [+ residual] rows of the training step,
 //                                    LN weight / bias gradients as fixed-order column reductions (no float atomics)
 //   gmr_rf_time_embed, gmr_rf_interp, gmr_rf_head_fwd / _prior_fwd / _bwd, gmr_rf_losses
@@ -133,11 +135,15 @@ __device__ __forceinline__ void cond_chunk(int64_t N, int64_t r0, const float* _
   tile_mm_ld<CK>(sT, LDH, W + K0, C, (tid >> 6) * 32, acc);
 }
 
-template <int C>
+// MIX: the evaluation's mix as the epilogue (base != nullptr at the entry); the plain instantiation reads none of
+// base, ldb, ratio and is the code it was before the mix existed
+template <int C, bool MIX>
 __global__ __launch_bounds__(256) void rf_sample_kernel(int64_t N, const float* __restrict__ z0, int64_t ldz,
                                                         const float* __restrict__ cond, int64_t ldc,
                                                         const float* __restrict__ P, RfOff o, int L, int n_steps,
-                                                        double dt_d, float* __restrict__ out, int64_t ldo) {
+                                                        double dt_d, float* __restrict__ out, int64_t ldo,
+                                                        const float* __restrict__ base, int64_t ldb,
+                                                        const float* __restrict__ ratio) {
   __shared__ __attribute__((aligned(16))) float sH[TR * LDH];
   __shared__ __attribute__((aligned(16))) float sT[TR * LDH];
   __shared__ __attribute__((aligned(16))) float sC[TR * LDH];
@@ -212,9 +218,24 @@ __global__ __launch_bounds__(256) void rf_sample_kernel(int64_t N, const float* 
     }
     __syncthreads();
   }
-  for (int idx = tid; idx < TR * D; idx += 256) {
-    const int r = idx / D, c = idx % D;
-    if (r0 + r < N) out[(r0 + r) * ldo + c] = sZ[r * LDZ + c];
+  if constexpr (!MIX) {  // plain: the integrated rows
+    for (int idx = tid; idx < TR * D; idx += 256) {
+      const int r = idx / D, c = idx % D;
+      if (r0 + r < N) out[(r0 + r) * ldo + c] = sZ[r * LDZ + c];
+    }
+  } else {
+    // the mix as the epilogue: out = base + ratio z, one fused multiply-add per element; z itself is not written.
+    // 16 lanes hold a row as one float4 each (sZ's rows are 16-byte aligned: LDZ % 4 == 0)
+    const float rt = ratio[0];
+    for (int idx = tid; idx < TR * (D / 4); idx += 256) {
+      const int r = idx / (D / 4), c = (idx % (D / 4)) * 4;
+      if (r0 + r < N) {
+        const float4 z = *reinterpret_cast<const float4*>(sZ + r * LDZ + c);
+        const float4 b = *reinterpret_cast<const float4*>(base + (r0 + r) * ldb + c);
+        *reinterpret_cast<float4*>(out + (r0 + r) * ldo + c) =
+            make_float4(fmaf(rt, z.x, b.x), fmaf(rt, z.y, b.y), fmaf(rt, z.z, b.z), fmaf(rt, z.w, b.w));
+      }
+    }
   }
 }
 
@@ -550,29 +571,59 @@ extern "C" int64_t gmr_rf_param_floats(int32_t C, int32_t L) {
   return rf_offsets(C, L).total;
 }
 
-extern "C" int gmr_rf_sample(int64_t N, int32_t hidden, int32_t C, int32_t L, int32_t n_steps, const float* z0,
-                             int64_t ldz, const float* cond, int64_t ldc, const float* params, float* out, int64_t ldo,
-                             void* stream) {
-  GMR_ARG(hidden == H, "rf_hidden_dim must be 128");
-  GMR_ARG(C == 64 || C == 128 || C == 192, "condition_dim must be 64, 128 or 192");
-  GMR_ARG(L >= 1 && L <= MAX_L, "rf_n_layers must be in 1..4");
-  GMR_ARG(N >= 1 && N <= ((int64_t)1 << 31) * TR - TR && n_steps >= 1, "N >= 1 and n_steps >= 1");
-  GMR_ARG(z0 && cond && params && out && ldz >= D && ldc >= C && ldo >= D, "bad pointers or strides");
-  GMR_ARG(((uintptr_t)params & 15) == 0, "params must be 16-byte aligned");
+// the argument checks both sampler entries share, reported under the entry's own name
+#define RF_SAMPLE_ARGS()                                                                                   \
+  GMR_ARG(hidden == H, "rf_hidden_dim must be 128");                                                       \
+  GMR_ARG(C == 64 || C == 128 || C == 192, "condition_dim must be 64, 128 or 192");                        \
+  GMR_ARG(L >= 1 && L <= MAX_L, "rf_n_layers must be in 1..4");                                            \
+  GMR_ARG(N >= 1 && N <= ((int64_t)1 << 31) * TR - TR && n_steps >= 1, "N >= 1 and n_steps >= 1");         \
+  GMR_ARG(z0 && cond && params && out && ldz >= D && ldc >= C && ldo >= D, "bad pointers or strides");     \
+  GMR_ARG(((uintptr_t)params & 15) == 0, "params must be 16-byte aligned")
+
+// gmr_rf_sample (base == nullptr) and gmr_rf_sample_mix behind one launch
+static int rf_sample_launch(int64_t N, int32_t C, int32_t L, int32_t n_steps, const float* z0, int64_t ldz,
+                            const float* cond, int64_t ldc, const float* params, float* out, int64_t ldo,
+                            const float* base, int64_t ldb, const float* ratio, void* stream) {
   const RfOff o = rf_offsets(C, L);
   const dim3 grid((unsigned)((N + TR - 1) / TR));
   const double dt = 1.0 / (double)n_steps;
-  if (C == 64)
-    hipLaunchKernelGGL(rf_sample_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, N, z0, ldz, cond, ldc, params, o,
-                       L, n_steps, dt, out, ldo);
-  else if (C == 128)
-    hipLaunchKernelGGL(rf_sample_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, N, z0, ldz, cond, ldc, params,
-                       o, L, n_steps, dt, out, ldo);
-  else
-    hipLaunchKernelGGL(rf_sample_kernel<192>, grid, dim3(256), 0, (hipStream_t)stream, N, z0, ldz, cond, ldc, params,
-                       o, L, n_steps, dt, out, ldo);
+#define RF_SAMPLE_LAUNCH(CW, MIXED)                                                                                 \
+  hipLaunchKernelGGL((rf_sample_kernel<CW, MIXED>), grid, dim3(256), 0, (hipStream_t)stream, N, z0, ldz, cond, ldc, \
+                     params, o, L, n_steps, dt, out, ldo, base, ldb, ratio)
+  if (base == nullptr) {
+    if (C == 64) RF_SAMPLE_LAUNCH(64, false);
+    else if (C == 128) RF_SAMPLE_LAUNCH(128, false);
+    else RF_SAMPLE_LAUNCH(192, false);
+  } else {
+    if (C == 64) RF_SAMPLE_LAUNCH(64, true);
+    else if (C == 128) RF_SAMPLE_LAUNCH(128, true);
+    else RF_SAMPLE_LAUNCH(192, true);
+  }
+#undef RF_SAMPLE_LAUNCH
   GMR_LAUNCHED();
   return GMR_OK;
+}
+
+extern "C" int gmr_rf_sample(int64_t N, int32_t hidden, int32_t C, int32_t L, int32_t n_steps, const float* z0,
+                             int64_t ldz, const float* cond, int64_t ldc, const float* params, float* out, int64_t ldo,
+                             void* stream) {
+  RF_SAMPLE_ARGS();
+  return rf_sample_launch(N, C, L, n_steps, z0, ldz, cond, ldc, params, out, ldo, nullptr, 0, nullptr, stream);
+}
+
+// out[r] = base[r] + ratio[0] * z[r] with z the rows gmr_rf_sample would write; base must not alias out (a tile's
+// rows are read as they are written, but nothing orders two calls' views of one table)
+extern "C" int gmr_rf_sample_mix(int64_t N, int32_t hidden, int32_t C, int32_t L, int32_t n_steps, const float* z0,
+                                 int64_t ldz, const float* cond, int64_t ldc, const float* params, const float* base,
+                                 int64_t ldb, const float* ratio, float* out, int64_t ldo, void* stream) {
+  RF_SAMPLE_ARGS();
+  GMR_ARG(base != nullptr, "base must not be null");
+  GMR_ARG(ratio != nullptr, "ratio must not be null (a device scalar)");
+  GMR_ARG(ldb >= D && ldb % 4 == 0, "the row stride of base must be >= 64 and a multiple of 4");
+  GMR_ARG(ldo >= D && ldo % 4 == 0, "the row stride of out must be >= 64 and a multiple of 4");
+  GMR_ARG(((uintptr_t)base & 15) == 0 && ((uintptr_t)out & 15) == 0, "base and out must be 16-byte aligned");
+  GMR_ARG(base != out, "base must not alias out");
+  return rf_sample_launch(N, C, L, n_steps, z0, ldz, cond, ldc, params, out, ldo, base, ldb, ratio, stream);
 }
 
 extern "C" int gmr_rf_act_fwd(int64_t N, const float* y, const float* ln_w, const float* ln_b, const float* res,

@@ -15,8 +15,11 @@
 //                        one with a row stride of its own: column blocks of abf and of saved in the model): Z =
 //                        (a + b + g f) / 3, the two segment means as for RFMGCN.  Writes the N x 64 prior and, on the
 //                        way, the N x 192 condition table [a | b | g f].
+//   gmr_rf_view_sum_prior  RFLGMRec (models/rflgmrec.py:125-143), from LGMRec's two propagated modal views mge_v, mge_t
+//                        (the column blocks of the one N x 128 table mge): Z = a + b, a sum and no mean of the views;
+//                        the segments, the grid and the fixed-order means as gmr_rf_view_prior.
 //
-// Three small kernels behind either entry point, each a template over the functor that forms Z for a row: per-block
+// Three small kernels behind every entry point, each a template over the functor that forms Z for a row: per-block
 // column sums of Z, the sum of a segment's block partials in one fixed order (one workgroup per segment), Z - mean.
 // The grid is ceil(U / 128) blocks of the first segment followed by ceil(I / 128) of the second, so no block holds
 // rows of both and the second segment starts at row U whatever U mod 128 is; gmr_rf_item_inputs has the first segment
@@ -66,6 +69,16 @@ struct ViewZ {
   int64_t ldb;
   __device__ __forceinline__ float4 operator()(int64_t row, int c) const {
     return gmr::f4_scale(0.5f, gmr::f4_add(ld4(a + row * lda + c), ld4(b + row * ldb + c)));
+  }
+};
+
+struct ViewSumZ {
+  const float* __restrict__ a;
+  int64_t lda;
+  const float* __restrict__ b;
+  int64_t ldb;
+  __device__ __forceinline__ float4 operator()(int64_t row, int c) const {
+    return gmr::f4_add(ld4(a + row * lda + c), ld4(b + row * ldb + c));
   }
 };
 
@@ -221,6 +234,28 @@ extern "C" int gmr_rf_view_prior(int64_t U, int64_t I, const float* a, int64_t l
   const int nbu = gmr::grid_for(U, RB), nbi = gmr::grid_for(I, RB);
   float* mean = ws + (int64_t)(nbu + nbi) * D;  // [users | items]
   const ViewZ z{a, lda, b, ldb};
+  hipLaunchKernelGGL(rf_prior_sum_kernel, dim3(nbu + nbi), dim3(256), 0, (hipStream_t)stream, nbu, U, U + I, z, ws);
+  GMR_LAUNCHED();
+  hipLaunchKernelGGL(rf_prior_mean_kernel<16>, dim3(2), dim3(16 * D), 0, (hipStream_t)stream, nbu, nbi, U, I, ws, mean);
+  GMR_LAUNCHED();
+  hipLaunchKernelGGL(rf_prior_sub_kernel, dim3(nbu + nbi), dim3(256), 0, (hipStream_t)stream, nbu, U, U + I, z, mean,
+                     prior, ldp);
+  GMR_LAUNCHED();
+  return GMR_OK;
+}
+
+extern "C" int64_t gmr_rf_view_sum_prior_ws_floats(int64_t U, int64_t I) { return gmr_rf_view_prior_ws_floats(U, I); }
+
+extern "C" int gmr_rf_view_sum_prior(int64_t U, int64_t I, const float* a, int64_t lda, const float* b, int64_t ldb,
+                                     float* prior, int64_t ldp, float* ws, void* stream) {
+  GMR_ARG(U >= 1 && I >= 1 && U <= MAX_ROWS && I <= MAX_ROWS, "1 <= U, I <= 2^31 - 128 (a mean over no rows is NaN)");
+  GMR_ARG(a && b && prior && ws && lda >= D && ldb >= D && ldp >= D, "bad pointers or strides");
+  GMR_ARG(aligned16(a) && aligned16(b) && aligned16(prior) && aligned16(ws) && lda % 4 == 0 && ldb % 4 == 0 &&
+              ldp % 4 == 0,
+          "rows must be 16-byte aligned");
+  const int nbu = gmr::grid_for(U, RB), nbi = gmr::grid_for(I, RB);
+  float* mean = ws + (int64_t)(nbu + nbi) * D;  // [users | items]
+  const ViewSumZ z{a, lda, b, ldb};
   hipLaunchKernelGGL(rf_prior_sum_kernel, dim3(nbu + nbi), dim3(256), 0, (hipStream_t)stream, nbu, U, U + I, z, ws);
   GMR_LAUNCHED();
   hipLaunchKernelGGL(rf_prior_mean_kernel<16>, dim3(2), dim3(16 * D), 0, (hipStream_t)stream, nbu, nbi, U, I, ws, mean);

@@ -194,6 +194,7 @@ SIGNATURES = {
     "gmr_rf_param_floats": (I64, [I32, I32]),
     "gmr_rf_tile_rows": (I32, []),
     "gmr_rf_sample": (I32, [I64, I32, I32, I32, I32, P, I64, P, I64, P, P, I64, P]),
+    "gmr_rf_sample_mix": (I32, [I64, I32, I32, I32, I32, P, I64, P, I64, P, P, I64, P, P, I64, P]),
     "gmr_rf_act_fwd": (I32, [I64, P, P, P, P, P, F32, P, P, P, P]),
     "gmr_rf_act_parts_floats": (I64, [I64]),
     "gmr_rf_act_bwd": (I32, [I64, P, P, P, P, P, F32, P, P, P, P, P, P, P]),
@@ -206,6 +207,8 @@ SIGNATURES = {
     "gmr_rf_item_inputs": (I32, [I64, I64, P, I64, P, I64, P, I64, P, I64, P, P]),
     "gmr_rf_view_prior_ws_floats": (I64, [I64, I64]),
     "gmr_rf_view_prior": (I32, [I64, I64, P, I64, P, I64, P, I64, P, P]),
+    "gmr_rf_view_sum_prior_ws_floats": (I64, [I64, I64]),
+    "gmr_rf_view_sum_prior": (I32, [I64, I64, P, I64, P, I64, P, I64, P, P]),
     "gmr_rf_view3_inputs_ws_floats": (I64, [I64, I64]),
     "gmr_rf_view3_inputs": (I32, [I64, I64, P, I64, P, I64, P, I64, P, I64, P, I64, P, I64, P, P]),
     "gmr_rf_losses": (I32, [I64, P, I64, P, F32, P, P]),

@@ -281,6 +281,11 @@ class LGMRec(EmbeddingRecommender):
             raise ValueError(f"{what} must be 2 x {self.N} x {self.hyper_num}, got {tuple(x.shape)}")
         return x.to(self.device).contiguous()
 
+    def _cge_for_hyper(self, cge):
+        """The collaborative view the hypergraph block and the combine read, once cge and self.mge of this forward
+        stand: cge itself.  A model that mixes rows into it (gmr/rflgmrec.py) returns a table of its own."""
+        return cge
+
     def _forward(self, train=False, step=0, g=None, keep=None):
         """lgmrec.py:115-151 into self.all (and the rows the backward reads).  g: (2, N, H) float Gumbel draws
         [image; text] (user rows first) instead of Philox's; keep: (2, N, H) uint8 keep masks likewise."""
@@ -318,15 +323,16 @@ class LGMRec(EmbeddingRecommender):
                 self.norm_adj.spmm(dst, [(mge[:, :D],), (mge[:, D:],)])
             mge = dst
         self.mge = mge
-        # the hyperedge layers
+        # the hyperedge layers and the combine read hc; the backward is handed cge
+        hc = self._cge_for_hyper(cge)
         hi = self.h[U:]
-        xv = xt = cge[U:]
+        xv = xt = hc[U:]
         for l in range(self.n_hyper_layer):
             self._lat(I, hi, xv, xt, self.lats[l])
             if l < self.n_hyper_layer - 1:
                 self._apply(hi, self.lats[l], self.ilay[l], 0)
                 xv, xt = self.ilay[l][:, :D], self.ilay[l][:, D:]
-        _lib.call("gmr_lgm_combine_fwd", N, ptr(cge), D, ptr(mge), 2 * D, ptr(self.h), 2 * H, H, ptr(self.lats[-1]),
+        _lib.call("gmr_lgm_combine_fwd", N, ptr(hc), D, ptr(mge), 2 * D, ptr(self.h), 2 * H, H, ptr(self.lats[-1]),
                   self.alpha, ptr(self.all), D, ptr(self.CLN), ptr(self.nrmCL), ptr(self.nrm3), 0, stream())
         return cge
 

@@ -10,7 +10,8 @@ Supported: embedding_dim 64, rf_hidden_dim 128, rf_n_layers 1..4, C in {64, 128,
                the two sampled InfoNCE terms on the predicted end points; the backward through the same layers (dW =
                dY^T X, db = colsum(dY), dX = dY W; gmr_rf_act_bwd); one AdamW step on the velocity slab
   generate     the Euler integration in one launch (gmr_rf_sample), or composed per layer from the same kernels
-               (fused=False: the comparison path of scripts/rffreedom_step.py)
+               (fused=False: the comparison path of scripts/rffreedom_step.py); with base=, the evaluation's mix
+               base + ratio * rows as that launch's epilogue (gmr_rf_sample_mix)
 
 Random draws come from Philox streams keyed on (seed, step counter, site); each has an injected alternative.
 
@@ -24,7 +25,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import kernels as K
-from .abstract_recommender import config_seed, sort_plan
+from .abstract_recommender import config_seed, copy64, sort_plan
 from .kernels import ptr, stream
 from .slab import Slab
 
@@ -302,8 +303,11 @@ class RFGenerator(nn.Module):
 
     # ------------------------------------------------------------------ sampling
     @torch.no_grad()
-    def generate(self, cond, z0=None, n_steps=None, out=None, fused=None):
-        """generate() (:896-975): n_steps Euler steps of the net from z0 ~ N(0, 1); dropout and guidance off."""
+    def generate(self, cond, z0=None, n_steps=None, out=None, fused=None, base=None):
+        """generate() (:896-975): n_steps Euler steps of the net from z0 ~ N(0, 1); dropout and guidance off.  base
+        (N x 64 fp32, any row stride that is a multiple of 4, not out's table): out = base + inference_mix_ratio *
+        rows instead of the rows, the mix as the sampler's epilogue (gmr_rf_sample_mix, the ratio read from the
+        device scalar _ratio) or, fused=False, composed from the same entry points as the other RF models' mix."""
         N = cond.shape[0]
         n_steps = int(n_steps or self.sampling_steps)
         if z0 is None:
@@ -313,7 +317,22 @@ class RFGenerator(nn.Module):
             z0 = z0.to(self.dev).contiguous()
         if out is None:
             out = torch.empty((N, D), dtype=torch.float32, device=self.dev)
-        if self.fused if fused is None else fused:
+        fused = self.fused if fused is None else fused
+        if base is not None:
+            if base.dtype != torch.float32 or tuple(base.shape) != (N, D) or base.stride(1) != 1:
+                raise ValueError(f"base must be a {N} x {D} fp32 table with unit column stride")
+            if fused:
+                _lib.call("gmr_rf_sample_mix", N, H, self.C, self.L, n_steps, ptr(z0), z0.stride(0), ptr(cond),
+                          cond.stride(0), ptr(self.slab.data), ptr(base), base.stride(0), ptr(self._ratio), ptr(out),
+                          out.stride(0), stream())
+                return out
+            if not out.is_contiguous():
+                raise ValueError("the composed mix writes a contiguous N x 64 table")
+            gen = self._generate_composed(cond, z0, n_steps, torch.empty_like(out))
+            copy64(base, out)
+            _lib.call("gmr_axpy_dev_f32", N * D, ptr(self._ratio), ptr(gen), ptr(out), stream())
+            return out
+        if fused:
             _lib.call("gmr_rf_sample", N, H, self.C, self.L, n_steps, ptr(z0), z0.stride(0), ptr(cond),
                       cond.stride(0), ptr(self.slab.data), ptr(out), out.stride(0), stream())
             return out

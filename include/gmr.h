@@ -799,6 +799,15 @@ int32_t gmr_rf_tile_rows(void);                    /* rows a workgroup of gmr_rf
  * the range: GMR_ERR_ARG. */
 int gmr_rf_sample(int64_t N, int32_t hidden, int32_t C, int32_t L, int32_t n_steps, const float* z0, int64_t ldz,
                   const float* cond, int64_t ldc, const float* params, float* out, int64_t ldo, void* stream);
+/* The same launch with the evaluation's mix as its epilogue: out[r] = base[r] + ratio[0] * z[r] with z the rows
+ * gmr_rf_sample writes from the same arguments, one fused multiply-add per element; z itself is not written.  base
+ * N x 64 with a row stride ldb of its own, ratio a device scalar (read by the kernel, so a captured graph sees a
+ * changed ratio), out N x 64 (ldo); columns of out beyond 64 are not written.  base must not alias out.  A NULL base
+ * or ratio, ldb or ldo below 64 or no multiple of 4, base or out not 16-byte aligned: GMR_ERR_ARG, next to
+ * gmr_rf_sample's own. */
+int gmr_rf_sample_mix(int64_t N, int32_t hidden, int32_t C, int32_t L, int32_t n_steps, const float* z0, int64_t ldz,
+                      const float* cond, int64_t ldc, const float* params, const float* base, int64_t ldb,
+                      const float* ratio, float* out, int64_t ldo, void* stream);
 /* Rows of the training step over N x 128 contiguous tables:
  *   out = drop(silu(LN(y) [+ res])) [+ add1] [+ add2],  drop(x) = mask ? x * keep_scale : 0
  * ln_w == ln_b == NULL: no LayerNorm; res, mask, add1, add2 may be NULL.  Backward from dout = dL/dout: dy = dL/dy,
@@ -851,6 +860,12 @@ int gmr_rf_item_inputs(int64_t I, int64_t U, const float* T, int64_t ldt, const 
 int64_t gmr_rf_view_prior_ws_floats(int64_t U, int64_t I);
 int gmr_rf_view_prior(int64_t U, int64_t I, const float* a, int64_t lda, const float* b, int64_t ldb, float* prior,
                       int64_t ldp, float* ws, void* stream);
+/* RFLGMRec's prior (models/rflgmrec.py:125-143) from LGMRec's two propagated modal views a, b (the column blocks of
+ * the (U + I) x 128 table mge): Z = a + b, a sum and no mean of the views; the arguments, the segments, the grid,
+ * the fixed-order means, the limits and the workspace are gmr_rf_view_prior's. */
+int64_t gmr_rf_view_sum_prior_ws_floats(int64_t U, int64_t I);
+int gmr_rf_view_sum_prior(int64_t U, int64_t I, const float* a, int64_t lda, const float* b, int64_t ldb, float* prior,
+                          int64_t ldp, float* ws, void* stream);
 /* RFSMORE's RF inputs (models/rfsmore.py:165-195) from SMORE's three views a, b, f and the fusion preference gate g
  * of the step, dropout mask and scale included ((U + I) x 64 each, every one with a stride of its own: column blocks
  * of a 192-wide and a 448-wide table in the model): cond ((U + I) x 192, ldc) = [a | b | g f], the first two blocks
