@@ -287,6 +287,19 @@ SIGNATURES = {
     "gmr_lgm_dh": (I32, [I64, P, P, I64, P, I32, P, I64, P, P, I64, F32, F32, P, I64, I32, P]),
     "gmr_lgm_logit_bwd": (I32, [I64, I64, I32, P, I64, P, P, P, I64, P, I64, I32, P]),
     "gmr_lgm_reg": (I32, [I32, I64, P, I64, P, P, P, F32, P, I64, P, P]),
+    # GRCN
+    "gmr_grcn_max_blocks": (I32, []),
+    "gmr_grcn_max_layers": (I32, []),
+    "gmr_grcn_route_fwd": (I32, [I64, I32, I32, I32, P, P, P, I64, P, I64, I64, P, I32, P]),
+    "gmr_grcn_attn_fwd": (I32, [I64, I64, I64, I32, P, P, P, P, P, I64, P, I64, P, I64, P, I32, P]),
+    "gmr_grcn_refine_fwd": (I32, [I64, I64, I64, I32, P, P, P, P, P, P, P, P, I64, P, P, P, I32, P]),
+    "gmr_grcn_dw": (I32, [I64, I64, I64, P, P, P, P, P, I64, P, I64, P, I64, P, I64, P, I32, P]),
+    "gmr_grcn_refine_bwd": (I32, [I64, I64, I64, I32, P, P, P, P, P, P, P, P, I64, P, P, P, P, I64, I32, P]),
+    "gmr_grcn_attn_bwd_dst": (I32, [I64, I64, I64, I32, P, P, P, P, P, I64, P, I64, P, P, P, I64, P, P, I64, I32, P]),
+    "gmr_grcn_route_bwd_dst": (I32, [I64, I64, I32, I32, I32, P, P, P, I64, P, I64, I64, P, P, I64, P, P, P, P, P, I64, P, P,
+                                     I64, F32, F32, P, P, I64, I32, P]),
+    "gmr_grcn_bwd_src": (I32, [I64, I32, I32, P, P, P, P, P, P, P, P, P, P, P, I64, I32, P]),
+    "gmr_grcn_loss_rows": (I32, [I32, I64, I32, P, I64, P, I64, P, P, I64, P, P, P, F32, F32, P, P, I64, I32, P]),
 }
 
 _lib = None

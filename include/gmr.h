@@ -1213,6 +1213,75 @@ int gmr_lgm_logit_bwd(int64_t U, int64_t I, int32_t H, const float* dL, int64_t 
 int gmr_lgm_reg(int32_t B, int64_t U, const float* all, int64_t lda, const int32_t* users, const int32_t* pos,
                 const int32_t* neg, float coef, float* contrib, int64_t ldc, float* out, void* stream);
 
+/* ---------------------------------------------------------------- GRCN (models/grcn.py; csrc/grcn.hip)
+ * The train graph: the users' CSR (rowptr U + 1, col: items, E entries) and the items' CSC (trp I + 1, tcol: users) with
+ * the position maps csr2csc[e] / csc2csr[t] between the two list orders.  M (1 or 2) modalities sit side by side in
+ * 64-column blocks of every table: F (I x 64 M) the normalised item rows, P (U x 64 M) the preference rows.  Per-edge
+ * arrays of the 2E directed edges are [user-destination in CSR order | item-destination in CSC order], one per modality
+ * (stride 2E).  All rows 16-byte aligned, ld % 4 == 0.  Every kernel takes max_blocks (0: the default cap,
+ * gmr_grcn_max_blocks()) and gives the same bits under any grid; no float atomics.
+ * route_fwd: P holds R + 1 tables (stride pstride floats); table 0 = n(preference) is read, tables 1..R written,
+ *   p^(r+1)_u = n(p^r_u + sum_j softmax_j(<p^r_u, f_j>) f_j) over the user's items; nrmY (R x M x U) the clamped norms.
+ *   messages = 0: the users receive no message (the reference's routing edges point from the users to the items,
+ *   grcn.py:149-156), a round is p <- n(p); the same flag in route_bwd_dst, which then leaves RA / RD alone.
+ * attn_fwd: rep (N x 64 M) = x + h for user rows (over the CSR, sources F) and item rows (over the CSC, sources P),
+ *   alpha (M x 2E) the softmax values.
+ * refine_fwd: W[q] = relu(max_m alpha_m[q] conf[source(q), m]) (conf N x M, ld ldc), WT the same values at the
+ *   transposed edge's position, arg[q] = the winning modality + 2 where the ReLU pruned the edge.
+ * dw: dw[q] = <x[source], dx1[dest]> + <x1[source], g[dest]> over N x 64 tables (the sampled product of the two
+ *   weighted hops' backward).
+ * refine_bwd: dalpha (M x 2E) and dconf (N x M, every row written) from dw through the ReLU and the recorded argmax; a
+ *   node sums over its own edge list.
+ * attn_bwd_dst: t_k = dalpha_k + <drep_d, x_k>, ds_k = alpha_k (t_k - sum alpha t) into ds (M x 2E), dxd (N x 64 M) =
+ *   drep + sum_k ds_k x_k.
+ * route_bwd_dst: from dpR = d loss / d p^R, the R rounds in reverse with alpha recomputed from p^r: RA, RD (R x M x E,
+ *   CSR order) = alpha^r, ds^r; DY (R x U x 64 M packed) = d loss / d (p^r + h^r); dpref_m (U x 64) = the normalise
+ *   backward of d p^0 (nrm0: M x U clamped norms of the preference rows) + dense_m preference_m + regtab (U x 64 M,
+ *   may be NULL).
+ * bwd_src: out[s] (n x 64 M) += sum over T <= 8 terms and the entries k of row s of (ptr, idx, pos) of
+ *   A_t[m][pos_k] DH_t[idx_k] + DS_t[m][pos_k] XD_t[idx_k]  (per-modality array stride estride_t).
+ * loss_rows: terms[b] = -log sigmoid(<r_u, r_p - r_n>), terms[B + b] = the batch rows' share of the regulariser means;
+ *   contrib (3B x (128 + 128 M), rows [users | pos | neg]) = [d result (inv_norm) | reg_weight d id rows | reg_weight d
+ *   preference rows] for gmr_scatter_sorted_f32 through the plan of keys [users | U + pos | U + neg]. */
+int32_t gmr_grcn_max_blocks(void);
+int32_t gmr_grcn_max_layers(void);
+int gmr_grcn_route_fwd(int64_t U, int32_t R, int32_t M, int32_t messages, const int32_t* rowptr, const int32_t* col,
+                       const float* F, int64_t ldf, float* P, int64_t ldp, int64_t pstride, float* nrmY, int32_t max_blocks,
+                       void* stream);
+int gmr_grcn_attn_fwd(int64_t U, int64_t I, int64_t E, int32_t M, const int32_t* rowptr, const int32_t* col,
+                      const int32_t* trp, const int32_t* tcol, const float* P, int64_t ldp, const float* F, int64_t ldf,
+                      float* rep, int64_t ldr, float* alpha, int32_t max_blocks, void* stream);
+int gmr_grcn_refine_fwd(int64_t U, int64_t I, int64_t E, int32_t M, const int32_t* rowptr, const int32_t* col,
+                        const int32_t* trp, const int32_t* tcol, const int32_t* csr2csc, const int32_t* csc2csr,
+                        const float* alpha, const float* conf, int64_t ldc, float* W, float* WT, int32_t* arg,
+                        int32_t max_blocks, void* stream);
+int gmr_grcn_dw(int64_t U, int64_t I, int64_t E, const int32_t* rowptr, const int32_t* col, const int32_t* trp,
+                const int32_t* tcol, const float* x, int64_t ldx, const float* x1, int64_t ldx1, const float* dx1,
+                int64_t lddx1, const float* g, int64_t ldg, float* dw, int32_t max_blocks, void* stream);
+int gmr_grcn_refine_bwd(int64_t U, int64_t I, int64_t E, int32_t M, const int32_t* rowptr, const int32_t* col,
+                        const int32_t* trp, const int32_t* tcol, const int32_t* csr2csc, const int32_t* csc2csr,
+                        const float* alpha, const float* conf, int64_t ldc, const int32_t* arg, const float* dw,
+                        float* dalpha, float* dconf, int64_t lddc, int32_t max_blocks, void* stream);
+int gmr_grcn_attn_bwd_dst(int64_t U, int64_t I, int64_t E, int32_t M, const int32_t* rowptr, const int32_t* col,
+                          const int32_t* trp, const int32_t* tcol, const float* P, int64_t ldp, const float* F,
+                          int64_t ldf, const float* alpha, const float* dalpha, const float* drep, int64_t lddr,
+                          float* ds, float* dxd, int64_t lddx, int32_t max_blocks, void* stream);
+int gmr_grcn_route_bwd_dst(int64_t U, int64_t E, int32_t R, int32_t M, int32_t messages, const int32_t* rowptr,
+                           const int32_t* col,
+                           const float* F, int64_t ldf, const float* P, int64_t ldp, int64_t pstride,
+                           const float* nrmY, const float* dpR, int64_t lddp, float* RA, float* RD, float* DY,
+                           const float* pref0, const float* pref1, int64_t ldpref, const float* nrm0,
+                           const float* regtab, int64_t ldreg, float dense0, float dense1, float* dpref0, float* dpref1,
+                           int64_t lddpref, int32_t max_blocks, void* stream);
+int gmr_grcn_bwd_src(int64_t n, int32_t M, int32_t T, const int32_t* ptr, const int32_t* idx, const int32_t* pos,
+                     const float* const* A, const float* const* DS, const int64_t* estride, const float* const* DH,
+                     const int64_t* lddh, const float* const* XD, const int64_t* ldxd, float* out, int64_t ldo,
+                     int32_t max_blocks, void* stream);
+int gmr_grcn_loss_rows(int32_t B, int64_t U, int32_t M, const float* res, int64_t ldr, const float* E, int64_t lde,
+                       const float* pref0, const float* pref1, int64_t ldpref, const int32_t* users, const int32_t* pos,
+                       const int32_t* neg, float inv_norm, float reg_weight, float* terms, float* contrib, int64_t ldc,
+                       int32_t max_blocks, void* stream);
+
 /* (Round 5's native executor of a captured HIP graph, gmr_graph_exec_*, was removed in round 6: its replayed
  * step ran slower on the GPU than eager issue; the host tape of gmr/tape.py removes the Python issue cost and
  * keeps the eager streams and order.) */
