@@ -1,5 +1,8 @@
 // Rectified-flow embedding generator (models/rf_modules.py of the reference: SimpleVelocityNet,
-// RFEmbeddingGenerator) for embedding_dim 64, hidden_dim 128, condition_dim 64, 128 or 192.
+// RFEmbeddingGenerator) for hidden_dim 128 and (embedding_dim, condition_dim) = (64, 64 | 128 | 192), (128, 128) or
+// (192, 192).  The entry points without a suffix are the embedding_dim 64 ones; the _w ones take the width DW as an
+// argument (the concat-fusion backbones generate rows as wide as their conditions) and are the same kernels
+// instantiated at DW: at DW = 64 both names reach the same code.
 //
 //   gmr_rf_sample                    the whole Euler integration of generate() in one launch: a workgroup owns
 //                                    32 rows, activations stay in LDS, weights are read through L2, products on
@@ -20,7 +23,8 @@
 namespace {
 using gmr::wave_sum;
 
-constexpr int H = 128, D = 64, TR = 32, LDH = H + 4, LDZ = D + 4;
+constexpr int H = 128, D = 64, TR = 32, LDH = H + 4;
+constexpr int MAX_DW = 192;  // widest generated row
 constexpr int MAX_L = 4;
 constexpr float LN_EPS = 1e-5f;
 
@@ -30,21 +34,26 @@ struct RfOff {
   int ow, ob, og, obe, pw, pb, total;
 };
 
-RfOff rf_offsets(int C, int L) {
+RfOff rf_offsets(int DW, int C, int L) {
   RfOff o{};
   int p = 0;
   auto take = [&](int n) { int at = p; p += n; return at; };
   o.tw = take(H * 64), o.tb = take(H);
   o.cw = take(H * C), o.cb = take(H), o.cg = take(H), o.cbe = take(H);
-  o.iw = take(H * D), o.ib = take(H), o.ig = take(H), o.ibe = take(H);
+  o.iw = take(H * DW), o.ib = take(H), o.ig = take(H), o.ibe = take(H);
   for (int l = 0; l < L; ++l) {
     o.blk[l][0] = take(H * H), o.blk[l][1] = take(H), o.blk[l][2] = take(H), o.blk[l][3] = take(H);
     o.blk[l][4] = take(H * H), o.blk[l][5] = take(H), o.blk[l][6] = take(H), o.blk[l][7] = take(H);
   }
   o.ow = take(H * H), o.ob = take(H), o.og = take(H), o.obe = take(H);
-  o.pw = take(D * H), o.pb = take(D);
+  o.pw = take(DW * H), o.pb = take(DW);
   o.total = p;
   return o;
+}
+
+// the (embedding_dim, condition_dim) pairs the kernels are instantiated for
+bool rf_widths_ok(int DW, int C) {
+  return (DW == 64 && (C == 64 || C == 128 || C == 192)) || (DW == 128 && C == 128) || (DW == 192 && C == 192);
 }
 
 __device__ __forceinline__ float silu(float x) { return x / (1.f + expf(-x)); }
@@ -135,24 +144,38 @@ __device__ __forceinline__ void cond_chunk(int64_t N, int64_t r0, const float* _
   tile_mm_ld<CK>(sT, LDH, W + K0, C, (tid >> 6) * 32, acc);
 }
 
+// LDS of one workgroup at generated width DW: three 32 x 132 activation tiles, the 32 x (DW + 4) z tile (row stride
+// mod 32 banks = 4 at every DW), the time embedding and its sinusoid: 58.75 KB at DW = 64 (static), 66.75 KB at 128 and
+// 74.75 KB at 192 (dynamic: past the 64 KB static limit; two workgroups still fit the 160 KB of a CU)
+constexpr int rf_sample_lds_floats(int DW) { return 3 * TR * LDH + TR * (DW + 4) + H + 64; }
+
 // MIX: the evaluation's mix as the epilogue (base != nullptr at the entry); the plain instantiation reads none of
-// base, ldb, ratio and is the code it was before the mix existed
-template <int C, bool MIX>
+// base, ldb, ratio and is the code it was before the mix existed.  DW: the width of z0, out and base.
+template <int DW, int C, bool MIX>
 __global__ __launch_bounds__(256) void rf_sample_kernel(int64_t N, const float* __restrict__ z0, int64_t ldz,
                                                         const float* __restrict__ cond, int64_t ldc,
                                                         const float* __restrict__ P, RfOff o, int L, int n_steps,
                                                         double dt_d, float* __restrict__ out, int64_t ldo,
                                                         const float* __restrict__ base, int64_t ldb,
                                                         const float* __restrict__ ratio) {
-  __shared__ __attribute__((aligned(16))) float sH[TR * LDH];
-  __shared__ __attribute__((aligned(16))) float sT[TR * LDH];
-  __shared__ __attribute__((aligned(16))) float sC[TR * LDH];
-  __shared__ __attribute__((aligned(16))) float sZ[TR * LDZ];
-  __shared__ float sE[H], sS[64];
+  static_assert(DW % 64 == 0 && DW <= MAX_DW, "whole 32-column output tiles, float4 rows");
+  constexpr int LDZ = DW + 4;
+  float *sH, *sT, *sC, *sZ, *sE, *sS;
+  if constexpr (DW == D) {
+    __shared__ __attribute__((aligned(16))) float aH[TR * LDH];
+    __shared__ __attribute__((aligned(16))) float aT[TR * LDH];
+    __shared__ __attribute__((aligned(16))) float aC[TR * LDH];
+    __shared__ __attribute__((aligned(16))) float aZ[TR * LDZ];
+    __shared__ float aE[H], aS[64];
+    sH = aH, sT = aT, sC = aC, sZ = aZ, sE = aE, sS = aS;
+  } else {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    sH = lds, sT = sH + TR * LDH, sC = sT + TR * LDH, sZ = sC + TR * LDH, sE = sZ + TR * LDZ, sS = sE + H;
+  }
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int64_t r0 = (int64_t)blockIdx.x * TR;
-  for (int idx = tid; idx < TR * D; idx += 256) {
-    const int r = idx / D, c = idx % D;
+  for (int idx = tid; idx < TR * DW; idx += 256) {
+    const int r = idx / DW, c = idx % DW;
     sZ[r * LDZ + c] = r0 + r < N ? z0[(r0 + r) * ldz + c] : 0.f;
   }
   // condition encoder, once per tile.  sT holds at most H condition columns, so the product runs in K chunks of
@@ -181,7 +204,7 @@ __global__ __launch_bounds__(256) void rf_sample_kernel(int64_t N, const float* 
     }
     // input projection; h = input + time + condition
     acc = zero16();
-    tile_mm<D>(sZ, LDZ, P + o.iw, w * 32, acc);
+    tile_mm<DW>(sZ, LDZ, P + o.iw, w * 32, acc);
     tile_store(sT, w * 32, acc, P + o.ib);
     __syncthreads();
     tile_ln_silu(sT, P + o.ig, P + o.ibe, nullptr, sE, sC, sH);
@@ -204,10 +227,12 @@ __global__ __launch_bounds__(256) void rf_sample_kernel(int64_t N, const float* 
     tile_store(sT, w * 32, acc, P + o.ob);
     __syncthreads();
     tile_ln_silu(sT, P + o.og, P + o.obe, nullptr, nullptr, nullptr, sT);
-    if (w < 2) {  // 64 output columns: z += v dt
+    // DW output columns in DW / 32 column tiles, tile ct on wave ct & 3 (waves 0, 1 alone at DW = 64): z += v dt.
+    // sZ is written here and read by the next step's input projection, behind the barrier that ends the step
+    for (int ct = w; ct < DW / 32; ct += 4) {
       acc = zero16();
-      tile_mm<H>(sT, LDH, P + o.pw, w * 32, acc);
-      const int hh = lane >> 5, c = w * 32 + (lane & 31);
+      tile_mm<H>(sT, LDH, P + o.pw, ct * 32, acc);
+      const int hh = lane >> 5, c = ct * 32 + (lane & 31);
       const float pb = P[o.pb + c];
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
@@ -219,16 +244,16 @@ __global__ __launch_bounds__(256) void rf_sample_kernel(int64_t N, const float* 
     __syncthreads();
   }
   if constexpr (!MIX) {  // plain: the integrated rows
-    for (int idx = tid; idx < TR * D; idx += 256) {
-      const int r = idx / D, c = idx % D;
+    for (int idx = tid; idx < TR * DW; idx += 256) {
+      const int r = idx / DW, c = idx % DW;
       if (r0 + r < N) out[(r0 + r) * ldo + c] = sZ[r * LDZ + c];
     }
   } else {
     // the mix as the epilogue: out = base + ratio z, one fused multiply-add per element; z itself is not written.
-    // 16 lanes hold a row as one float4 each (sZ's rows are 16-byte aligned: LDZ % 4 == 0)
+    // DW / 4 lanes hold a row as one float4 each (sZ's rows are 16-byte aligned: LDZ % 4 == 0)
     const float rt = ratio[0];
-    for (int idx = tid; idx < TR * (D / 4); idx += 256) {
-      const int r = idx / (D / 4), c = (idx % (D / 4)) * 4;
+    for (int idx = tid; idx < TR * (DW / 4); idx += 256) {
+      const int r = idx / (DW / 4), c = (idx % (DW / 4)) * 4;
       if (r0 + r < N) {
         const float4 z = *reinterpret_cast<const float4*>(sZ + r * LDZ + c);
         const float4 b = *reinterpret_cast<const float4*>(base + (r0 + r) * ldb + c);
@@ -354,18 +379,22 @@ __global__ void rf_time_embed_kernel(int64_t N, const float* __restrict__ t, flo
   out[row * 64 + k] = sinf(a), out[row * 64 + 32 + k] = cosf(a);
 }
 
+// the row kernels below take the generated width DW as a template argument; DW = 64 is the code behind the entry
+// points without a suffix
+template <int DW>
 __global__ void rf_interp_kernel(int64_t N, const float* __restrict__ X1, int64_t ld1, const float* __restrict__ X0,
                                  const float* __restrict__ t, float* __restrict__ Xt) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N * D) return;
-  const int64_t row = i >> 6;
-  const int c = (int)(i & 63);
+  if (i >= N * DW) return;
+  const int64_t row = i / DW;
+  const int c = (int)(i % DW);
   const float tt = t[row];
   Xt[i] = tt * X1[row * ld1 + c] + (1.f - tt) * X0[i];
 }
 
 // one wave per row, lane = column: v += (1 - t)^2 scale cos_grad(Xt, X1); squared error to parts; pred.  PRIOR: the
-// user-prior term (1 - t)^2 pscale prior is added first, as the reference orders the two guidance terms
+// user-prior term (1 - t)^2 pscale prior is added first, as the reference orders the two guidance terms.  The 64-wide
+// head: the code behind gmr_rf_head_fwd / _prior_fwd, and behind the _w entries at DW = 64
 template <bool PRIOR>
 __global__ __launch_bounds__(256) void rf_head_fwd_kernel(int64_t N, float* __restrict__ V,
                                                           const float* __restrict__ Xt, const float* __restrict__ X1,
@@ -395,20 +424,67 @@ __global__ __launch_bounds__(256) void rf_head_fwd_kernel(int64_t N, float* __re
   pred[o] = xt + (1.f - tt) * v;
 }
 
+// The head at DW = 128 or 192: one wave per row, a lane holds the DW / 64 columns lane + 64 j.  Norms and dots are wave
+// sums over the whole row (a lane adds its columns in order first).  Every operation is rounded on its own (no
+// contraction), so the result does not depend on how an instantiation is compiled: with an all-zero prior the PRIOR
+// instantiation adds an exact zero and gives the plain one's bits.
+template <int DW, bool PRIOR>
+__global__ __launch_bounds__(256) void rf_head_fwd_w_kernel(int64_t N, float* __restrict__ V,
+                                                            const float* __restrict__ Xt,
+                                                            const float* __restrict__ X1, int64_t ld1,
+                                                            const float* __restrict__ X0, const float* __restrict__ t,
+                                                            const float* __restrict__ prior, int64_t ldp,
+                                                            float pscale, float gscale, float* __restrict__ pred,
+                                                            double* __restrict__ parts) {
+#pragma clang fp contract(off)
+  constexpr int NJ = DW / 64;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t o = row * DW + lane;
+  const float tt = t[row];
+  float xt[NJ], x1[NJ], x0[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) xt[j] = Xt[o + 64 * j], x1[j] = X1[row * ld1 + lane + 64 * j], x0[j] = X0[o + 64 * j];
+  float st = xt[0] * xt[0], s1 = x1[0] * x1[0], sd = xt[0] * x1[0];
+#pragma unroll
+  for (int j = 1; j < NJ; ++j) st += xt[j] * xt[j], s1 += x1[j] * x1[j], sd += xt[j] * x1[j];
+  const float nt = sqrtf(wave_sum(st)), n1 = sqrtf(wave_sum(s1));
+  const float dot = wave_sum(sd);
+  const float cs = dot / sqrtf(fmaxf((nt * nt) * (n1 * n1), 1e-16f));  // F.cosine_similarity, eps 1e-8
+  const float ntc = fmaxf(nt, 1e-8f);
+  const float lam = (1.f - tt) * (1.f - tt);
+  double sq = 0.0;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const float grad = (x1[j] / fmaxf(n1, 1e-12f)) / ntc - (xt[j] / fmaxf(nt, 1e-12f)) * cs / ntc;
+    float v = V[o + 64 * j];
+    if (PRIOR) v = v + lam * pscale * prior[row * ldp + lane + 64 * j];
+    v = v + lam * gscale * grad;
+    V[o + 64 * j] = v;
+    const float e = v - (x1[j] - x0[j]);
+    sq = j == 0 ? (double)e * (double)e : sq + (double)e * (double)e;
+    pred[o + 64 * j] = xt[j] + (1.f - tt) * v;
+  }
+  sq = gmr::wave_sum_d(sq);
+  if (lane == 0) parts[row] = sq;
+}
+
+template <int DW>
 __global__ void rf_head_bwd_kernel(int64_t N, const float* __restrict__ V, const float* __restrict__ X1, int64_t ld1,
                                    const float* __restrict__ X0, const float* __restrict__ t,
                                    const float* __restrict__ dpred, float inv, float* __restrict__ dV) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N * D) return;
-  const int64_t row = i >> 6;
-  const int c = (int)(i & 63);
+  if (i >= N * DW) return;
+  const int64_t row = i / DW;
+  const int c = (int)(i % DW);
   const float vt = X1[row * ld1 + c] - X0[i];
   dV[i] = 2.f * (V[i] - vt) * inv + (1.f - t[row]) * dpred[i];
 }
 
-// [rf_loss, cl_loss, total]: fixed-order fp64 sums by one block
-__global__ __launch_bounds__(256) void rf_losses_kernel(int64_t N, const double* __restrict__ rowparts, int64_t B,
-                                                        const double* __restrict__ clparts, float weight,
+// [rf_loss, cl_loss, total]: fixed-order fp64 sums by one block; rf_loss is the mean over the N x DW entries
+__global__ __launch_bounds__(256) void rf_losses_kernel(int64_t N, int DW, const double* __restrict__ rowparts,
+                                                        int64_t B, const double* __restrict__ clparts, float weight,
                                                         float* __restrict__ out) {
   __shared__ double red[2][4];
   double a = 0.0, c = 0.0;
@@ -418,7 +494,7 @@ __global__ __launch_bounds__(256) void rf_losses_kernel(int64_t N, const double*
   if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = a, red[1][threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float rf = (float)(((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (double)(N * D));
+    const float rf = (float)(((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (double)(N * DW));
     const float cl = B > 0 ? (float)(((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (double)B) : 0.f;
     out[0] = rf, out[1] = cl, out[2] = rf + weight * cl;
   }
@@ -438,9 +514,11 @@ __device__ __forceinline__ float4 across_groups(float4 v) {  // over the four 16
   return gmr::f4_add(v, gmr::shfl_xor_f4(v, 32));
 }
 
-// one block per anchor.  16 lanes hold a 64-column row as float4, so a wave reads four negatives at a time (and
-// draws four indices, not one index 64 times): slot s = 16 i + 4 w + q belongs to group q = lane >> 4 of wave w.
-// Group sums are butterflies, the four groups and then the four waves are added in order: one fixed order.
+// one block per anchor.  16 lanes hold a DW-column row as NJ = DW / 64 float4 each (columns 4 (lane & 15) + 64 j), so a
+// wave reads four negatives at a time (and draws four indices, not one index 64 times): slot s = 16 i + 4 w + q
+// belongs to group q = lane >> 4 of wave w.  A lane adds its NJ chunks in order, group sums are butterflies, the four
+// groups and then the four waves are added in order: one fixed order.
+template <int NJ>
 __global__ __launch_bounds__(256) void rf_infonce_kernel(int64_t n, const float* __restrict__ pred, int64_t ldp,
                                                          const float* __restrict__ T, int64_t ldt, int64_t row_off,
                                                          const int32_t* __restrict__ idx, int n_neg,
@@ -448,18 +526,31 @@ __global__ __launch_bounds__(256) void rf_infonce_kernel(int64_t n, const float*
                                                          uint64_t step, uint64_t site, float inv_temp, float coef,
                                                          double* __restrict__ parts, float* __restrict__ contrib,
                                                          int64_t ldc) {
-  __shared__ float4 rg[4][16], rq[4][16];
+  __shared__ float4 rg[4][NJ][16], rq[4][NJ][16];
   __shared__ float rs[4];
   const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6, q = lane >> 4, c = (lane & 15) * 4;
   const int64_t p = idx[b];
-  const float4 a = *reinterpret_cast<const float4*>(pred + (row_off + p) * ldp + c);
-  const float na = fmaxf(sqrtf(group16_sum(dot4(a, a))), 1e-12f);
-  const float4 an = make_float4(a.x / na, a.y / na, a.z / na, a.w / na);
-  const float4 tp = *reinterpret_cast<const float4*>(T + (row_off + p) * ldt + c);
-  const float ntp = fmaxf(sqrtf(group16_sum(dot4(tp, tp))), 1e-12f);
-  const float4 tpn = make_float4(tp.x / ntp, tp.y / ntp, tp.z / ntp, tp.w / ntp);
-  const float pos = expf(group16_sum(dot4(an, tpn)) * inv_temp);
-  auto row_of = [&](int s) -> const float4* {
+  auto dotj = [](const float4* x, const float4* y) {  // a lane's share of a row dot product
+    float d = dot4(x[0], y[0]);
+#pragma unroll
+    for (int j = 1; j < NJ; ++j) d += dot4(x[j], y[j]);
+    return d;
+  };
+  float4 a[NJ], an[NJ], tp[NJ], tpn[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    a[j] = *reinterpret_cast<const float4*>(pred + (row_off + p) * ldp + c + 64 * j);
+    tp[j] = *reinterpret_cast<const float4*>(T + (row_off + p) * ldt + c + 64 * j);
+  }
+  const float na = fmaxf(sqrtf(group16_sum(dotj(a, a))), 1e-12f);
+  const float ntp = fmaxf(sqrtf(group16_sum(dotj(tp, tp))), 1e-12f);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    an[j] = make_float4(a[j].x / na, a[j].y / na, a[j].z / na, a[j].w / na);
+    tpn[j] = make_float4(tp[j].x / ntp, tp[j].y / ntp, tp[j].z / ntp, tp[j].w / ntp);
+  }
+  const float pos = expf(group16_sum(dotj(an, tpn)) * inv_temp);
+  auto row_of = [&](int s) -> const float* {
     int64_t j;
     if (neg) {
       j = neg[(int64_t)b * n_neg + s];
@@ -470,43 +561,66 @@ __global__ __launch_bounds__(256) void rf_infonce_kernel(int64_t n, const float*
       j = (int64_t)(((uint64_t)x * (uint64_t)n) >> 32);
     }
     if (j == p) j = (j + 1) % n;  // a negative equal to the positive: the next row
-    return reinterpret_cast<const float4*>(T + (row_off + j) * ldt + c);
+    return T + (row_off + j) * ldt + c;
   };
-  // the reference normalises the gathered negatives (B, n_neg, 64) over dim 1, the n_neg axis (:762): column c of
+  // the reference normalises the gathered negatives (B, n_neg, DW) over dim 1, the n_neg axis (:762): column c of
   // every negative of this anchor is divided by the norm of that column over the anchor's negatives
-  float4 sq = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 sq[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) sq[j] = make_float4(0.f, 0.f, 0.f, 0.f);
   const int iters = (n_neg + 15) / 16;
   for (int i = 0; i < iters; ++i) {
     const int s = 16 * i + 4 * w + q;
     if (s < n_neg) {
-      const float4 tv = *row_of(s);
-      sq = gmr::f4_add(sq, mul4(tv, tv));
+      const float* tr = row_of(s);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const float4 tv = *reinterpret_cast<const float4*>(tr + 64 * j);
+        sq[j] = gmr::f4_add(sq[j], mul4(tv, tv));
+      }
     }
   }
-  sq = across_groups(sq);
-  if (lane < 16) rq[w][lane] = sq;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    sq[j] = across_groups(sq[j]);
+    if (lane < 16) rq[w][j][lane] = sq[j];
+  }
   __syncthreads();
-  const float4 cn = gmr::f4_add(gmr::f4_add(gmr::f4_add(rq[0][lane & 15], rq[1][lane & 15]), rq[2][lane & 15]),
-                                rq[3][lane & 15]);
-  const float4 icn = make_float4(1.f / fmaxf(sqrtf(cn.x), 1e-12f), 1.f / fmaxf(sqrtf(cn.y), 1e-12f),
-                                 1.f / fmaxf(sqrtf(cn.z), 1e-12f), 1.f / fmaxf(sqrtf(cn.w), 1e-12f));
-  float4 gv = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 icn[NJ], gv[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const float4 cn = gmr::f4_add(
+        gmr::f4_add(gmr::f4_add(rq[0][j][lane & 15], rq[1][j][lane & 15]), rq[2][j][lane & 15]), rq[3][j][lane & 15]);
+    icn[j] = make_float4(1.f / fmaxf(sqrtf(cn.x), 1e-12f), 1.f / fmaxf(sqrtf(cn.y), 1e-12f),
+                         1.f / fmaxf(sqrtf(cn.z), 1e-12f), 1.f / fmaxf(sqrtf(cn.w), 1e-12f));
+    gv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
   float se = 0.f;
   // every lane takes every iteration: the group sums are wave-wide shuffles
   for (int i = 0; i < iters; ++i) {
     const int s = 16 * i + 4 * w + q;
     const bool valid = s < n_neg;
-    float4 tn = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (valid) tn = mul4(*row_of(s), icn);
-    const float d = group16_sum(dot4(an, tn));
+    float4 tn[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) tn[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (valid) {
+      const float* tr = row_of(s);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) tn[j] = mul4(*reinterpret_cast<const float4*>(tr + 64 * j), icn[j]);
+    }
+    const float d = group16_sum(dotj(an, tn));
     const float e = valid ? expf(d * inv_temp) : 0.f;
     se += e;
-    gv = gmr::f4_fma(e, tn, gv);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) gv[j] = gmr::f4_fma(e, tn[j], gv[j]);
   }
-  gv = across_groups(gv);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    gv[j] = across_groups(gv[j]);
+    if (lane < 16) rg[w][j][lane] = gv[j];
+  }
   se += __shfl_xor(se, 16);
   se += __shfl_xor(se, 32);
-  if (lane < 16) rg[w][lane] = gv;
   if (lane == 0) rs[w] = se;
   __syncthreads();
   if (w != 0) return;
@@ -516,17 +630,24 @@ __global__ __launch_bounds__(256) void rf_infonce_kernel(int64_t n, const float*
   const float ttl = pos + nsum;
   if (lane == 0) parts[b] = (double)log1pf(nsum / pos);
   // d loss / d an = ((pos / ttl - 1) tp + sum_s (e_s / ttl) t_s) / temp, then through the normalisation
-  const float4 gs = gmr::f4_add(gmr::f4_add(gmr::f4_add(rg[0][lane & 15], rg[1][lane & 15]), rg[2][lane & 15]),
-                                rg[3][lane & 15]);
   const float k1 = -nsum / ttl, k2 = 1.f / ttl;
-  const float4 gn = make_float4((k1 * tpn.x + gs.x * k2) * inv_temp, (k1 * tpn.y + gs.y * k2) * inv_temp,
-                                (k1 * tpn.z + gs.z * k2) * inv_temp, (k1 * tpn.w + gs.w * k2) * inv_temp);
-  const float proj = group16_sum(dot4(an, gn));
+  float4 gn[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const float4 gs = gmr::f4_add(
+        gmr::f4_add(gmr::f4_add(rg[0][j][lane & 15], rg[1][j][lane & 15]), rg[2][j][lane & 15]), rg[3][j][lane & 15]);
+    gn[j] = make_float4((k1 * tpn[j].x + gs.x * k2) * inv_temp, (k1 * tpn[j].y + gs.y * k2) * inv_temp,
+                        (k1 * tpn[j].z + gs.z * k2) * inv_temp, (k1 * tpn[j].w + gs.w * k2) * inv_temp);
+  }
+  const float proj = group16_sum(dotj(an, gn));
   const float sc = coef / na;
-  if (lane < 16)
-    *reinterpret_cast<float4*>(contrib + (int64_t)b * ldc + c) =
-        make_float4(sc * (gn.x - an.x * proj), sc * (gn.y - an.y * proj), sc * (gn.z - an.z * proj),
-                    sc * (gn.w - an.w * proj));
+  if (lane < 16) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      *reinterpret_cast<float4*>(contrib + (int64_t)b * ldc + c + 64 * j) =
+          make_float4(sc * (gn[j].x - an[j].x * proj), sc * (gn[j].y - an[j].y * proj),
+                      sc * (gn[j].z - an[j].z * proj), sc * (gn[j].w - an[j].w * proj));
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ optimiser, draws
@@ -566,49 +687,91 @@ __global__ void rf_rand_kernel(int64_t n, uint64_t seed, uint64_t step, float* _
 // ==================================================================================================== C ABI
 extern "C" int32_t gmr_rf_tile_rows(void) { return TR; }
 
-extern "C" int64_t gmr_rf_param_floats(int32_t C, int32_t L) {
-  if ((C != 64 && C != 128 && C != 192) || L < 1 || L > MAX_L) return -1;
-  return rf_offsets(C, L).total;
+extern "C" int64_t gmr_rf_param_floats_w(int32_t DW, int32_t C, int32_t L) {
+  if (!rf_widths_ok(DW, C) || L < 1 || L > MAX_L) return -1;
+  return rf_offsets(DW, C, L).total;
 }
 
-// the argument checks both sampler entries share, reported under the entry's own name
+extern "C" int64_t gmr_rf_param_floats(int32_t C, int32_t L) { return gmr_rf_param_floats_w(D, C, L); }
+
+// the argument checks the sampler entries share, reported under the entry's own name; DW is the entry's width
 #define RF_SAMPLE_ARGS()                                                                                   \
   GMR_ARG(hidden == H, "rf_hidden_dim must be 128");                                                       \
-  GMR_ARG(C == 64 || C == 128 || C == 192, "condition_dim must be 64, 128 or 192");                        \
+  GMR_ARG(rf_widths_ok(DW, C),                                                                             \
+          "(embedding_dim, condition_dim) must be (64, 64 | 128 | 192), (128, 128) or (192, 192)");        \
   GMR_ARG(L >= 1 && L <= MAX_L, "rf_n_layers must be in 1..4");                                            \
   GMR_ARG(N >= 1 && N <= ((int64_t)1 << 31) * TR - TR && n_steps >= 1, "N >= 1 and n_steps >= 1");         \
-  GMR_ARG(z0 && cond && params && out && ldz >= D && ldc >= C && ldo >= D, "bad pointers or strides");     \
+  GMR_ARG(z0 && cond && params && out && ldz >= DW && ldc >= C && ldo >= DW, "bad pointers or strides");   \
   GMR_ARG(((uintptr_t)params & 15) == 0, "params must be 16-byte aligned")
 
-// gmr_rf_sample (base == nullptr) and gmr_rf_sample_mix behind one launch
-static int rf_sample_launch(int64_t N, int32_t C, int32_t L, int32_t n_steps, const float* z0, int64_t ldz,
+#define RF_MIX_ARGS()                                                                                               \
+  GMR_ARG(base != nullptr, "base must not be null");                                                                \
+  GMR_ARG(ratio != nullptr, "ratio must not be null (a device scalar)");                                            \
+  GMR_ARG(ldb >= DW && ldb % 4 == 0, "the row stride of base must be >= the row width and a multiple of 4");        \
+  GMR_ARG(ldo >= DW && ldo % 4 == 0, "the row stride of out must be >= the row width and a multiple of 4");         \
+  GMR_ARG(((uintptr_t)base & 15) == 0 && ((uintptr_t)out & 15) == 0, "base and out must be 16-byte aligned");       \
+  GMR_ARG(base != out, "base must not alias out")
+
+// one instantiation: the wide ones take their LDS as dynamic (past the 64 KB static limit), which the runtime grants
+// per kernel and device on request; the request is a host call without a launch, made before every wide launch
+template <int DW, int C, bool MIX>
+static hipError_t rf_sample_one(dim3 grid, hipStream_t st, int64_t N, const float* z0, int64_t ldz, const float* cond,
+                                int64_t ldc, const float* params, const RfOff& o, int L, int n_steps, double dt,
+                                float* out, int64_t ldo, const float* base, int64_t ldb, const float* ratio) {
+  int lds = 0;
+  if (DW != D) {
+    lds = rf_sample_lds_floats(DW) * (int)sizeof(float);
+    const hipError_t e = hipFuncSetAttribute((const void*)rf_sample_kernel<DW, C, MIX>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((rf_sample_kernel<DW, C, MIX>), grid, dim3(256), lds, st, N, z0, ldz, cond, ldc, params, o, L,
+                     n_steps, dt, out, ldo, base, ldb, ratio);
+  return hipGetLastError();
+}
+
+// the plain (base == nullptr) and the mixed sampler of every width behind one launch
+static int rf_sample_launch(int64_t N, int32_t DW, int32_t C, int32_t L, int32_t n_steps, const float* z0, int64_t ldz,
                             const float* cond, int64_t ldc, const float* params, float* out, int64_t ldo,
                             const float* base, int64_t ldb, const float* ratio, void* stream) {
-  const RfOff o = rf_offsets(C, L);
+  const RfOff o = rf_offsets(DW, C, L);
   const dim3 grid((unsigned)((N + TR - 1) / TR));
   const double dt = 1.0 / (double)n_steps;
-#define RF_SAMPLE_LAUNCH(CW, MIXED)                                                                                 \
-  hipLaunchKernelGGL((rf_sample_kernel<CW, MIXED>), grid, dim3(256), 0, (hipStream_t)stream, N, z0, ldz, cond, ldc, \
-                     params, o, L, n_steps, dt, out, ldo, base, ldb, ratio)
+  hipError_t e;
+#define RF_SAMPLE_LAUNCH(DWW, CW, MIXED)                                                                          \
+  e = rf_sample_one<DWW, CW, MIXED>(grid, (hipStream_t)stream, N, z0, ldz, cond, ldc, params, o, L, n_steps, dt, \
+                                    out, ldo, base, ldb, ratio)
   if (base == nullptr) {
-    if (C == 64) RF_SAMPLE_LAUNCH(64, false);
-    else if (C == 128) RF_SAMPLE_LAUNCH(128, false);
-    else RF_SAMPLE_LAUNCH(192, false);
+    if (DW == 128) RF_SAMPLE_LAUNCH(128, 128, false);
+    else if (DW == 192) RF_SAMPLE_LAUNCH(192, 192, false);
+    else if (C == 64) RF_SAMPLE_LAUNCH(64, 64, false);
+    else if (C == 128) RF_SAMPLE_LAUNCH(64, 128, false);
+    else RF_SAMPLE_LAUNCH(64, 192, false);
   } else {
-    if (C == 64) RF_SAMPLE_LAUNCH(64, true);
-    else if (C == 128) RF_SAMPLE_LAUNCH(128, true);
-    else RF_SAMPLE_LAUNCH(192, true);
+    if (DW == 128) RF_SAMPLE_LAUNCH(128, 128, true);
+    else if (DW == 192) RF_SAMPLE_LAUNCH(192, 192, true);
+    else if (C == 64) RF_SAMPLE_LAUNCH(64, 64, true);
+    else if (C == 128) RF_SAMPLE_LAUNCH(64, 128, true);
+    else RF_SAMPLE_LAUNCH(64, 192, true);
   }
 #undef RF_SAMPLE_LAUNCH
-  GMR_LAUNCHED();
+  if (e != hipSuccess) return gmr::hip_status(__func__, e);
   return GMR_OK;
 }
 
 extern "C" int gmr_rf_sample(int64_t N, int32_t hidden, int32_t C, int32_t L, int32_t n_steps, const float* z0,
                              int64_t ldz, const float* cond, int64_t ldc, const float* params, float* out, int64_t ldo,
                              void* stream) {
+  constexpr int DW = D;
   RF_SAMPLE_ARGS();
-  return rf_sample_launch(N, C, L, n_steps, z0, ldz, cond, ldc, params, out, ldo, nullptr, 0, nullptr, stream);
+  return rf_sample_launch(N, DW, C, L, n_steps, z0, ldz, cond, ldc, params, out, ldo, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int gmr_rf_sample_w(int64_t N, int32_t hidden, int32_t DW, int32_t C, int32_t L, int32_t n_steps,
+                               const float* z0, int64_t ldz, const float* cond, int64_t ldc, const float* params,
+                               float* out, int64_t ldo, void* stream) {
+  RF_SAMPLE_ARGS();
+  return rf_sample_launch(N, DW, C, L, n_steps, z0, ldz, cond, ldc, params, out, ldo, nullptr, 0, nullptr, stream);
 }
 
 // out[r] = base[r] + ratio[0] * z[r] with z the rows gmr_rf_sample would write; base must not alias out (a tile's
@@ -616,14 +779,19 @@ extern "C" int gmr_rf_sample(int64_t N, int32_t hidden, int32_t C, int32_t L, in
 extern "C" int gmr_rf_sample_mix(int64_t N, int32_t hidden, int32_t C, int32_t L, int32_t n_steps, const float* z0,
                                  int64_t ldz, const float* cond, int64_t ldc, const float* params, const float* base,
                                  int64_t ldb, const float* ratio, float* out, int64_t ldo, void* stream) {
+  constexpr int DW = D;
   RF_SAMPLE_ARGS();
-  GMR_ARG(base != nullptr, "base must not be null");
-  GMR_ARG(ratio != nullptr, "ratio must not be null (a device scalar)");
-  GMR_ARG(ldb >= D && ldb % 4 == 0, "the row stride of base must be >= 64 and a multiple of 4");
-  GMR_ARG(ldo >= D && ldo % 4 == 0, "the row stride of out must be >= 64 and a multiple of 4");
-  GMR_ARG(((uintptr_t)base & 15) == 0 && ((uintptr_t)out & 15) == 0, "base and out must be 16-byte aligned");
-  GMR_ARG(base != out, "base must not alias out");
-  return rf_sample_launch(N, C, L, n_steps, z0, ldz, cond, ldc, params, out, ldo, base, ldb, ratio, stream);
+  RF_MIX_ARGS();
+  return rf_sample_launch(N, DW, C, L, n_steps, z0, ldz, cond, ldc, params, out, ldo, base, ldb, ratio, stream);
+}
+
+extern "C" int gmr_rf_sample_mix_w(int64_t N, int32_t hidden, int32_t DW, int32_t C, int32_t L, int32_t n_steps,
+                                   const float* z0, int64_t ldz, const float* cond, int64_t ldc, const float* params,
+                                   const float* base, int64_t ldb, const float* ratio, float* out, int64_t ldo,
+                                   void* stream) {
+  RF_SAMPLE_ARGS();
+  RF_MIX_ARGS();
+  return rf_sample_launch(N, DW, C, L, n_steps, z0, ldz, cond, ldc, params, out, ldo, base, ldb, ratio, stream);
 }
 
 extern "C" int gmr_rf_act_fwd(int64_t N, const float* y, const float* ln_w, const float* ln_b, const float* res,
@@ -662,20 +830,72 @@ extern "C" int gmr_rf_time_embed(int64_t N, const float* t, float* out, void* st
   return GMR_OK;
 }
 
+// the row entries of every width: DISPATCH_DW(launch) instantiates at the three widths
+#define RF_DW_OK(DW) ((DW) == 64 || (DW) == 128 || (DW) == 192)
+#define RF_DISPATCH_DW(DW, LAUNCH) \
+  do {                             \
+    if ((DW) == 64) {              \
+      LAUNCH(64);                  \
+    } else if ((DW) == 128) {      \
+      LAUNCH(128);                 \
+    } else {                       \
+      LAUNCH(192);                 \
+    }                              \
+  } while (0)
+
+extern "C" int gmr_rf_interp_w(int64_t N, int32_t DW, const float* X1, int64_t ld1, const float* X0, const float* t,
+                               float* Xt, void* stream) {
+  GMR_ARG(RF_DW_OK(DW), "the row width must be 64, 128 or 192");
+  GMR_ARG(N >= 1 && X1 && X0 && t && Xt && ld1 >= DW, "bad args");
+#define LAUNCH(W)                                                                                                      \
+  hipLaunchKernelGGL(rf_interp_kernel<W>, dim3(gmr::grid_for(N * W, 256)), dim3(256), 0, (hipStream_t)stream, N, X1, \
+                     ld1, X0, t, Xt)
+  RF_DISPATCH_DW(DW, LAUNCH);
+#undef LAUNCH
+  GMR_LAUNCHED();
+  return GMR_OK;
+}
+
 extern "C" int gmr_rf_interp(int64_t N, const float* X1, int64_t ld1, const float* X0, const float* t, float* Xt,
                              void* stream) {
-  GMR_ARG(N >= 1 && X1 && X0 && t && Xt && ld1 >= D, "bad args");
-  hipLaunchKernelGGL(rf_interp_kernel, dim3(gmr::grid_for(N * D, 256)), dim3(256), 0, (hipStream_t)stream, N, X1, ld1,
-                     X0, t, Xt);
+  return gmr_rf_interp_w(N, D, X1, ld1, X0, t, Xt, stream);
+}
+
+extern "C" int gmr_rf_head_fwd_w(int64_t N, int32_t DW, float* V, const float* Xt, const float* X1, int64_t ld1,
+                                 const float* X0, const float* t, float guidance_scale, float* pred, double* row_parts,
+                                 void* stream) {
+  GMR_ARG(RF_DW_OK(DW), "the row width must be 64, 128 or 192");
+  GMR_ARG(N >= 1 && V && Xt && X1 && X0 && t && pred && row_parts && ld1 >= DW, "bad args");
+#define LAUNCH(KERNEL)                                                                                           \
+  hipLaunchKernelGGL((KERNEL), dim3(gmr::grid_for(N, 4)), dim3(256), 0, (hipStream_t)stream, N, V, Xt, X1, ld1, X0, t, \
+                     (const float*)nullptr, (int64_t)0, 0.f, guidance_scale, pred, row_parts)
+  if (DW == D) LAUNCH(rf_head_fwd_kernel<false>);
+  else if (DW == 128) LAUNCH((rf_head_fwd_w_kernel<128, false>));
+  else LAUNCH((rf_head_fwd_w_kernel<192, false>));
+#undef LAUNCH
   GMR_LAUNCHED();
   return GMR_OK;
 }
 
 extern "C" int gmr_rf_head_fwd(int64_t N, float* V, const float* Xt, const float* X1, int64_t ld1, const float* X0,
                                const float* t, float guidance_scale, float* pred, double* row_parts, void* stream) {
-  GMR_ARG(N >= 1 && V && Xt && X1 && X0 && t && pred && row_parts && ld1 >= D, "bad args");
-  hipLaunchKernelGGL(rf_head_fwd_kernel<false>, dim3(gmr::grid_for(N, 4)), dim3(256), 0, (hipStream_t)stream, N, V, Xt,
-                     X1, ld1, X0, t, (const float*)nullptr, (int64_t)0, 0.f, guidance_scale, pred, row_parts);
+  return gmr_rf_head_fwd_w(N, D, V, Xt, X1, ld1, X0, t, guidance_scale, pred, row_parts, stream);
+}
+
+extern "C" int gmr_rf_head_prior_fwd_w(int64_t N, int32_t DW, float* V, const float* Xt, const float* X1, int64_t ld1,
+                                       const float* X0, const float* t, const float* prior, int64_t ldp,
+                                       float prior_scale, float cos_scale, float* pred, double* row_parts,
+                                       void* stream) {
+  GMR_ARG(RF_DW_OK(DW), "the row width must be 64, 128 or 192");
+  GMR_ARG(N >= 1 && V && Xt && X1 && X0 && t && pred && row_parts && ld1 >= DW, "bad args");
+  GMR_ARG(prior && ldp >= DW, "prior must be a table as wide as the rows with a row stride >= that width");
+#define LAUNCH(KERNEL)                                                                                           \
+  hipLaunchKernelGGL((KERNEL), dim3(gmr::grid_for(N, 4)), dim3(256), 0, (hipStream_t)stream, N, V, Xt, X1, ld1, X0, t, \
+                     prior, ldp, prior_scale, cos_scale, pred, row_parts)
+  if (DW == D) LAUNCH(rf_head_fwd_kernel<true>);
+  else if (DW == 128) LAUNCH((rf_head_fwd_w_kernel<128, true>));
+  else LAUNCH((rf_head_fwd_w_kernel<192, true>));
+#undef LAUNCH
   GMR_LAUNCHED();
   return GMR_OK;
 }
@@ -684,28 +904,59 @@ extern "C" int gmr_rf_head_prior_fwd(int64_t N, float* V, const float* Xt, const
                                      const float* X0, const float* t, const float* prior, int64_t ldp,
                                      float prior_scale, float cos_scale, float* pred, double* row_parts,
                                      void* stream) {
-  GMR_ARG(N >= 1 && V && Xt && X1 && X0 && t && pred && row_parts && ld1 >= D, "bad args");
-  GMR_ARG(prior && ldp >= D, "prior must be an N x 64 table with a row stride >= 64");
-  hipLaunchKernelGGL(rf_head_fwd_kernel<true>, dim3(gmr::grid_for(N, 4)), dim3(256), 0, (hipStream_t)stream, N, V, Xt,
-                     X1, ld1, X0, t, prior, ldp, prior_scale, cos_scale, pred, row_parts);
+  return gmr_rf_head_prior_fwd_w(N, D, V, Xt, X1, ld1, X0, t, prior, ldp, prior_scale, cos_scale, pred, row_parts,
+                                 stream);
+}
+
+extern "C" int gmr_rf_head_bwd_w(int64_t N, int32_t DW, const float* V, const float* X1, int64_t ld1, const float* X0,
+                                 const float* t, const float* dpred, float* dV, void* stream) {
+  GMR_ARG(RF_DW_OK(DW), "the row width must be 64, 128 or 192");
+  GMR_ARG(N >= 1 && V && X1 && X0 && t && dpred && dV && ld1 >= DW, "bad args");
+#define LAUNCH(W)                                                                                                      \
+  hipLaunchKernelGGL(rf_head_bwd_kernel<W>, dim3(gmr::grid_for(N * W, 256)), dim3(256), 0, (hipStream_t)stream, N, V, \
+                     X1, ld1, X0, t, dpred, (float)(1.0 / ((double)N * W)), dV)
+  RF_DISPATCH_DW(DW, LAUNCH);
+#undef LAUNCH
   GMR_LAUNCHED();
   return GMR_OK;
 }
 
 extern "C" int gmr_rf_head_bwd(int64_t N, const float* V, const float* X1, int64_t ld1, const float* X0, const float* t,
                                const float* dpred, float* dV, void* stream) {
-  GMR_ARG(N >= 1 && V && X1 && X0 && t && dpred && dV && ld1 >= D, "bad args");
-  hipLaunchKernelGGL(rf_head_bwd_kernel, dim3(gmr::grid_for(N * D, 256)), dim3(256), 0, (hipStream_t)stream, N, V, X1,
-                     ld1, X0, t, dpred, (float)(1.0 / ((double)N * D)), dV);
+  return gmr_rf_head_bwd_w(N, D, V, X1, ld1, X0, t, dpred, dV, stream);
+}
+
+extern "C" int gmr_rf_losses_w(int64_t N, int32_t DW, const double* row_parts, int64_t B, const double* cl_parts,
+                               float weight, float* out3, void* stream) {
+  GMR_ARG(RF_DW_OK(DW), "the row width must be 64, 128 or 192");
+  GMR_ARG(N >= 1 && row_parts && B >= 0 && (B == 0 || cl_parts) && out3, "bad args");
+  hipLaunchKernelGGL(rf_losses_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, N, (int)DW, row_parts, B, cl_parts,
+                     weight, out3);
   GMR_LAUNCHED();
   return GMR_OK;
 }
 
 extern "C" int gmr_rf_losses(int64_t N, const double* row_parts, int64_t B, const double* cl_parts, float weight,
                              float* out3, void* stream) {
-  GMR_ARG(N >= 1 && row_parts && B >= 0 && (B == 0 || cl_parts) && out3, "bad args");
-  hipLaunchKernelGGL(rf_losses_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, N, row_parts, B, cl_parts, weight,
-                     out3);
+  return gmr_rf_losses_w(N, D, row_parts, B, cl_parts, weight, out3, stream);
+}
+
+extern "C" int gmr_rf_infonce_sampled_fwd_bwd_w(int32_t B, int64_t n, int32_t DW, const float* pred, int64_t ldp,
+                                                const float* target, int64_t ldt, int64_t row_off, const int32_t* idx,
+                                                int32_t n_neg, const int32_t* neg, uint64_t seed, uint64_t step,
+                                                uint64_t site, float inv_temp, float coef, double* parts,
+                                                float* contrib, int64_t ldc, void* stream) {
+  GMR_ARG(RF_DW_OK(DW), "the row width must be 64, 128 or 192");
+  GMR_ARG(B >= 1 && n >= 1 && n < ((int64_t)1 << 31) && n_neg >= 0 && row_off >= 0, "bad sizes");
+  GMR_ARG(pred && target && idx && parts && contrib && ldp >= DW && ldt >= DW && ldc >= DW, "bad pointers or strides");
+  GMR_ARG((((uintptr_t)pred | (uintptr_t)target | (uintptr_t)contrib) & 15) == 0 && ldp % 4 == 0 && ldt % 4 == 0 &&
+              ldc % 4 == 0,
+          "rows must be 16-byte aligned");
+#define LAUNCH(W)                                                                                                   \
+  hipLaunchKernelGGL(rf_infonce_kernel<W / 64>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, n, pred, ldp, \
+                     target, ldt, row_off, idx, n_neg, neg, seed, step, site, inv_temp, coef, parts, contrib, ldc)
+  RF_DISPATCH_DW(DW, LAUNCH);
+#undef LAUNCH
   GMR_LAUNCHED();
   return GMR_OK;
 }
@@ -715,15 +966,8 @@ extern "C" int gmr_rf_infonce_sampled_fwd_bwd(int32_t B, int64_t n, const float*
                                               const int32_t* neg, uint64_t seed, uint64_t step, uint64_t site,
                                               float inv_temp, float coef, double* parts, float* contrib, int64_t ldc,
                                               void* stream) {
-  GMR_ARG(B >= 1 && n >= 1 && n < ((int64_t)1 << 31) && n_neg >= 0 && row_off >= 0, "bad sizes");
-  GMR_ARG(pred && target && idx && parts && contrib && ldp >= D && ldt >= D && ldc >= D, "bad pointers or strides");
-  GMR_ARG((((uintptr_t)pred | (uintptr_t)target | (uintptr_t)contrib) & 15) == 0 && ldp % 4 == 0 && ldt % 4 == 0 &&
-              ldc % 4 == 0,
-          "rows must be 16-byte aligned");
-  hipLaunchKernelGGL(rf_infonce_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, n, pred, ldp, target, ldt,
-                     row_off, idx, n_neg, neg, seed, step, site, inv_temp, coef, parts, contrib, ldc);
-  GMR_LAUNCHED();
-  return GMR_OK;
+  return gmr_rf_infonce_sampled_fwd_bwd_w(B, n, D, pred, ldp, target, ldt, row_off, idx, n_neg, neg, seed, step, site,
+                                          inv_temp, coef, parts, contrib, ldc, stream);
 }
 
 extern "C" int gmr_adamw_f32(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,

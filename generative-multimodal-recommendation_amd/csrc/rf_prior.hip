@@ -18,6 +18,10 @@
 //   gmr_rf_view_sum_prior  RFLGMRec (models/rflgmrec.py:125-143), from LGMRec's two propagated modal views mge_v, mge_t
 //                        (the column blocks of the one N x 128 table mge): Z = a + b, a sum and no mean of the views;
 //                        the segments, the grid and the fixed-order means as gmr_rf_view_prior.
+//   gmr_rf_center_segments  RFGRCN (models/rfgrcn.py:171-190), from GRCN's concatenated table [id_rep | rep_v | rep_t]
+//                        (N x W, W = 64, 128 or 192): every 64-wide block centred per segment, which is the whole
+//                        W-wide row minus its segment's column means.  The same three kernels at row width W (a lane
+//                        holds W / 64 float4 of a row), so the table is read once per pass, not once per block.
 //
 // Three small kernels behind every entry point, each a template over the functor that forms Z for a row: per-block
 // column sums of Z, the sum of a segment's block partials in one fixed order (one workgroup per segment), Z - mean.
@@ -188,6 +192,104 @@ __global__ __launch_bounds__(256) void rf_prior_sub_kernel(int nbu, int64_t U, i
   }
 }
 
+// ------------------------------------------------------------------------------------------------ W-wide rows
+// The three kernels above at row width W = 64 NJ for a plain table: 16 lanes hold a row as NJ float4 each (columns
+// 4 (lane & 15) + 64 j), the grid and the block's row order are the same, parts and mean rows are W wide.
+template <int NJ>
+__global__ __launch_bounds__(256) void rf_center_sum_kernel(int nbu, int64_t U, int64_t N,
+                                                            const float* __restrict__ src, int64_t lds,
+                                                            float* __restrict__ parts) {
+  __shared__ float4 red[16][NJ][16];
+  const int rg = threadIdx.x >> 4, l = threadIdx.x & 15, c = l * 4;
+  int64_t lo, hi;
+  block_rows(nbu, U, N, lo, hi);
+  float4 acc[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int i = 0; i < RB / 16; ++i) {
+    const int64_t row = lo + i * 16 + rg;
+    if (row < hi) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[j] = gmr::f4_add(acc[j], ld4(src + row * lds + c + D * j));
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) red[rg][j][l] = acc[j];
+  __syncthreads();
+  if (threadIdx.x < 16 * NJ) {  // thread (j, l) adds the 16 row groups in order
+    const int j = threadIdx.x >> 4;
+    float4 s = red[0][j][l];
+#pragma unroll
+    for (int g = 1; g < 16; ++g) s = gmr::f4_add(s, red[g][j][l]);
+    st4(parts + (int64_t)blockIdx.x * (D * NJ) + D * j + c, s);
+  }
+}
+
+// mean[seg][c] over W = 64 NJ columns by one workgroup of 1024 threads per segment: thread (part, c), part < MP =
+// 1024 / W, adds the segment's blocks part, part + MP, ... in order, the MP parts are added in order
+template <int NJ>
+__global__ __launch_bounds__(1024) void rf_center_mean_kernel(int nbu, int nbi, int64_t U, int64_t I,
+                                                              const float* __restrict__ parts,
+                                                              float* __restrict__ mean) {
+  constexpr int W = D * NJ, MP = 1024 / W;
+  __shared__ float red[MP][W];
+  const int seg = blockIdx.x, c = threadIdx.x % W, part = threadIdx.x / W;
+  const int nblk = seg ? nbi : nbu;
+  const float* p = parts + (int64_t)(seg ? nbu : 0) * W;
+  if (part < MP) {
+    float s = 0.f;
+    for (int i = part; i < nblk; i += MP) s += p[(int64_t)i * W + c];
+    red[part][c] = s;
+  }
+  __syncthreads();
+  if (part == 0) {
+    float t = red[0][c];
+#pragma unroll
+    for (int k = 1; k < MP; ++k) t += red[k][c];
+    mean[seg * W + c] = t / (float)(seg ? I : U);
+  }
+}
+
+template <int NJ>
+__global__ __launch_bounds__(256) void rf_center_sub_kernel(int nbu, int64_t U, int64_t N,
+                                                            const float* __restrict__ src, int64_t lds,
+                                                            const float* __restrict__ mean, float* __restrict__ prior,
+                                                            int64_t ldp) {
+  const int rg = threadIdx.x >> 4, c = (threadIdx.x & 15) * 4;
+  int64_t lo, hi;
+  const int seg = block_rows(nbu, U, N, lo, hi);
+  float4 m[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) m[j] = ld4(mean + seg * (D * NJ) + D * j + c);
+#pragma unroll
+  for (int i = 0; i < RB / 16; ++i) {
+    const int64_t row = lo + i * 16 + rg;
+    if (row < hi) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const float4 v = ld4(src + row * lds + c + D * j);
+        st4(prior + row * ldp + c + D * j, make_float4(v.x - m[j].x, v.y - m[j].y, v.z - m[j].z, v.w - m[j].w));
+      }
+    }
+  }
+}
+
+template <int NJ>
+hipError_t center_launch(int nbu, int nbi, int64_t U, int64_t I, const float* src, int64_t lds, float* prior,
+                         int64_t ldp, float* ws, hipStream_t st) {
+  float* mean = ws + (int64_t)(nbu + nbi) * (D * NJ);  // [users | items]
+  hipLaunchKernelGGL(rf_center_sum_kernel<NJ>, dim3(nbu + nbi), dim3(256), 0, st, nbu, U, U + I, src, lds, ws);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(rf_center_mean_kernel<NJ>, dim3(2), dim3(1024), 0, st, nbu, nbi, U, I, ws, mean);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(rf_center_sub_kernel<NJ>, dim3(nbu + nbi), dim3(256), 0, st, nbu, U, U + I, src, lds, mean, prior,
+                     ldp);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // ==================================================================================================== C ABI
@@ -289,5 +391,26 @@ extern "C" int gmr_rf_view3_inputs(int64_t U, int64_t I, const float* a, int64_t
   hipLaunchKernelGGL(rf_prior_sub_kernel, dim3(nbu + nbi), dim3(256), 0, (hipStream_t)stream, nbu, U, U + I,
                      View3Z<false>{a, lda, b, ldb, f, ldf, g, ldg, nullptr, 0}, mean, prior, ldp);
   GMR_LAUNCHED();
+  return GMR_OK;
+}
+
+extern "C" int64_t gmr_rf_center_segments_ws_floats(int64_t U, int64_t I, int32_t W) {
+  if (U < 1 || I < 1 || U > MAX_ROWS || I > MAX_ROWS || (W != D && W != 2 * D && W != 3 * D)) return -1;
+  return ((U + RB - 1) / RB + (I + RB - 1) / RB + 2) * W;
+}
+
+extern "C" int gmr_rf_center_segments(int64_t U, int64_t I, int32_t W, const float* src, int64_t lds, float* prior,
+                                      int64_t ldp, float* ws, void* stream) {
+  GMR_ARG(U >= 1 && I >= 1 && U <= MAX_ROWS && I <= MAX_ROWS, "1 <= U, I <= 2^31 - 128 (a mean over no rows is NaN)");
+  GMR_ARG(W == D || W == 2 * D || W == 3 * D, "the row width W must be 64, 128 or 192");
+  GMR_ARG(src && prior && ws && lds >= W && ldp >= W, "bad pointers or strides");
+  GMR_ARG(aligned16(src) && aligned16(prior) && aligned16(ws) && lds % 4 == 0 && ldp % 4 == 0,
+          "rows must be 16-byte aligned");
+  const int nbu = gmr::grid_for(U, RB), nbi = gmr::grid_for(I, RB);
+  const hipStream_t st = (hipStream_t)stream;
+  const hipError_t e = W == D       ? center_launch<1>(nbu, nbi, U, I, src, lds, prior, ldp, ws, st)
+                       : W == 2 * D ? center_launch<2>(nbu, nbi, U, I, src, lds, prior, ldp, ws, st)
+                                    : center_launch<3>(nbu, nbi, U, I, src, lds, prior, ldp, ws, st);
+  if (e != hipSuccess) return gmr::hip_status(__func__, e);
   return GMR_OK;
 }

@@ -214,6 +214,19 @@ SIGNATURES = {
     "gmr_rf_losses": (I32, [I64, P, I64, P, F32, P, P]),
     "gmr_rf_infonce_sampled_fwd_bwd": (I32, [I32, I64, P, I64, P, I64, I64, P, I32, P, U64, U64, U64, F32, F32, P, P,
                                              I64, P]),
+    # the generator at row width DW (64, 128, 192)
+    "gmr_rf_param_floats_w": (I64, [I32, I32, I32]),
+    "gmr_rf_sample_w": (I32, [I64, I32, I32, I32, I32, I32, P, I64, P, I64, P, P, I64, P]),
+    "gmr_rf_sample_mix_w": (I32, [I64, I32, I32, I32, I32, I32, P, I64, P, I64, P, P, I64, P, P, I64, P]),
+    "gmr_rf_interp_w": (I32, [I64, I32, P, I64, P, P, P, P]),
+    "gmr_rf_head_fwd_w": (I32, [I64, I32, P, P, P, I64, P, P, F32, P, P, P]),
+    "gmr_rf_head_prior_fwd_w": (I32, [I64, I32, P, P, P, I64, P, P, P, I64, F32, F32, P, P, P]),
+    "gmr_rf_head_bwd_w": (I32, [I64, I32, P, P, I64, P, P, P, P, P]),
+    "gmr_rf_losses_w": (I32, [I64, I32, P, I64, P, F32, P, P]),
+    "gmr_rf_infonce_sampled_fwd_bwd_w": (I32, [I32, I64, I32, P, I64, P, I64, I64, P, I32, P, U64, U64, U64, F32, F32,
+                                               P, P, I64, P]),
+    "gmr_rf_center_segments_ws_floats": (I64, [I64, I64, I32]),
+    "gmr_rf_center_segments": (I32, [I64, I64, I32, P, I64, P, I64, P, P]),
     "gmr_adamw_f32": (I32, [I64, P, P, P, P, F32, F32, F32, F32, F32, F32, P]),
     "gmr_rf_randn": (I32, [I64, U64, U64, U64, P, P]),
     "gmr_rf_rand": (I32, [I64, U64, U64, U64, P, P]),

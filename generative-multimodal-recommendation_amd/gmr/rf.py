@@ -1,8 +1,10 @@
 """Rectified-flow embedding generator on MI355X — models/rf_modules.py of the reference (RFEmbeddingGenerator with
-SimpleVelocityNet), backbone-agnostic: a backbone hands it the detached target table X1 ((U + I) x 64) and the
+SimpleVelocityNet), backbone-agnostic: a backbone hands it the detached target table X1 ((U + I) x D) and the
 condition table ((U + I) x C) and mixes generate()'s output into its evaluation embeddings.
 
-Supported: embedding_dim 64, rf_hidden_dim 128, rf_n_layers 1..4, C in {64, 128, 192}, 1-RF (use_2rf False).
+Supported: rf_hidden_dim 128, rf_n_layers 1..4, 1-RF (use_2rf False), and (embedding_dim D, condition_dim C) = (64,
+64 | 128 | 192), or D = C = 128 or 192 for the concat-fusion backbones, whose generated rows are as wide as their
+conditions.  At D != 64 the same steps run on the width-taking entry points (gmr_rf_*_w); "64" below reads D there.
 
   train_step   X0 ~ N(0, 1), t ~ U[0, 1), X_t; the velocity net forward with saved pre-activations (the Linear
                layers on the GEMM with the BIAS epilogue, gmr_rf_act_fwd rows between them); the guidance / MSE head
@@ -35,8 +37,8 @@ GUIDANCE_SCALE = 0.1  # cosine_guidance_scale; cosine_decay_power 2 is in the ke
 PRIOR_SCALE = 0.2  # user_guidance_scale (guidance_decay_power 2 likewise): the constructor defaults, no backbone sets them
 
 
-def param_specs(C, n_layers):
-    """(name, shape) of velocity_net.named_parameters() in the reference's order."""
+def param_specs(C, n_layers, D=D):
+    """(name, shape) of velocity_net.named_parameters() in the reference's order; D: embedding_dim."""
     out = [("time_embed.1.weight", (H, 64)), ("time_embed.1.bias", (H,))]
     for m, k in (("condition_encoder", C), ("input_proj", D)):
         out += [(f"{m}.0.weight", (H, k)), (f"{m}.0.bias", (H,)), (f"{m}.1.weight", (H,)), (f"{m}.1.bias", (H,))]
@@ -75,12 +77,14 @@ def check_config(config):
 class RFGenerator(nn.Module):
     def __init__(self, n_users, n_items, condition_dim, device, n_layers=2, dropout=0.1, learning_rate=1e-4,
                  sampling_steps=10, warmup_epochs=5, inference_mix_ratio=0.2, contrast_temp=0.2, contrast_weight=1.0,
-                 n_negatives=1024, weight_decay=0.01, seed=0, fused=True):
+                 n_negatives=1024, weight_decay=0.01, seed=0, fused=True, embedding_dim=D):
         super().__init__()
-        C, L = int(condition_dim), int(n_layers)
-        if int(_lib.load().gmr_rf_param_floats(C, L)) < 0:
-            raise NotImplementedError(f"condition_dim {C} / rf_n_layers {L}: the kernels take 64, 128 or 192 and 1..4")
-        self.U, self.I, self.N, self.C, self.L = int(n_users), int(n_items), int(n_users + n_items), C, L
+        C, L, Dw = int(condition_dim), int(n_layers), int(embedding_dim)
+        if int(_lib.load().gmr_rf_param_floats_w(Dw, C, L)) < 0:
+            raise NotImplementedError(f"embedding_dim {Dw} / condition_dim {C} / rf_n_layers {L}: the kernels take "
+                                      f"condition_dim 64, 128 or 192 at embedding_dim 64, or both 128 or both 192, "
+                                      f"and 1..4 layers")
+        self.U, self.I, self.N, self.C, self.L, self.D = int(n_users), int(n_items), int(n_users + n_items), C, L, Dw
         self.dev = device
         self.dropout, self.lr, self.wd = float(dropout), float(learning_rate), float(weight_decay)
         self.betas, self.eps = (0.9, 0.999), 1e-8
@@ -89,9 +93,9 @@ class RFGenerator(nn.Module):
         self.temp, self.weight, self.n_neg = float(contrast_temp), float(contrast_weight), int(n_negatives)
         self.seed, self.fused = int(seed), bool(fused)
         self.step_ctr, self.epoch = 0, 0
-        self.specs = param_specs(C, L)
+        self.specs = param_specs(C, L, Dw)
         self.slab = Slab([(n, sh, None) for n, sh in self.specs], device)
-        assert self.slab.numel == int(_lib.load().gmr_rf_param_floats(C, L)), "the slab is the kernel's packed layout"
+        assert self.slab.numel == int(_lib.load().gmr_rf_param_floats_w(Dw, C, L)), "the slab is the kernel's packed layout"
         # nn.Linear / nn.LayerNorm default initialisation
         with torch.no_grad():
             for name, sh in self.specs:
@@ -128,11 +132,18 @@ class RFGenerator(nn.Module):
     def param_views(self):
         return [self.slab.view(n) for n, _ in self.specs]
 
+    def _rf(self, name, *args, at=1):
+        """An RF entry point at this generator's width: `name` itself at 64, else `name`_w with the width as the
+        argument at position `at`."""
+        if self.D == D:
+            return _lib.call(name, *args)
+        return _lib.call(name + "_w", *args[:at], self.D, *args[at:])
+
     # ------------------------------------------------------------------ buffers
     def _work(self, B):
         w = self._w
         if w is None or w["B"] < B:
-            N, dev = self.N, self.dev
+            N, dev, D = self.N, self.dev, self.D
             f = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)  # noqa: E731
             w = {"B": B, "X0": f(N, D), "t": f(N), "Xt": f(N, D), "S": f(N, 64), "V": f(N, D), "pred": f(N, D),
                  "dpred": f(N, D), "dV": f(N, D), "G1": f(N, H), "G2": f(N, H), "GH": f(N, H), "GR": f(N, H),
@@ -191,8 +202,8 @@ class RFGenerator(nn.Module):
         return 1.0 / (1.0 - self.dropout) if self.dropout > 0.0 else 1.0
 
     def _net_fwd(self, w, x, S, cond, masks):
-        """The velocity net on x (N x 64) with the time features S (N x 64); pre-activations in w["Y"], layer
-        outputs in w["A"] (the block outputs h_l are A["input"], A["block{l}b"]); returns V (N x 64)."""
+        """The velocity net on x (N x D) with the time features S (N x 64); pre-activations in w["Y"], layer
+        outputs in w["A"] (the block outputs h_l are A["input"], A["block{l}b"]); returns V (N x D)."""
         Y, A = w["Y"], w["A"]
         mk = {site: self._mask(w, site, masks, i) for i, site in enumerate(self._sites()) if not site.endswith("b")}
         w["mk"] = mk
@@ -239,10 +250,10 @@ class RFGenerator(nn.Module):
     # ------------------------------------------------------------------ training
     def infonce(self, pred, target, row_off, n, idx, parts, contrib, neg=None, site=0, coef=1.0):
         """Sampled InfoNCE of B anchors of one side (gmr_rf_infonce_sampled_fwd_bwd)."""
-        _lib.call("gmr_rf_infonce_sampled_fwd_bwd", idx.numel(), n, ptr(pred), pred.stride(0), ptr(target),
-                  target.stride(0), row_off, ptr(idx), neg.shape[1] if neg is not None else self.n_neg, ptr(neg),
-                  self.seed, self.step_ctr, site, 1.0 / self.temp, float(coef), ptr(parts), ptr(contrib),
-                  contrib.stride(0), stream())
+        self._rf("gmr_rf_infonce_sampled_fwd_bwd", idx.numel(), n, ptr(pred), pred.stride(0), ptr(target),
+                 target.stride(0), row_off, ptr(idx), neg.shape[1] if neg is not None else self.n_neg, ptr(neg),
+                 self.seed, self.step_ctr, site, 1.0 / self.temp, float(coef), ptr(parts), ptr(contrib),
+                 contrib.stride(0), stream(), at=2)
 
     def train_step(self, X1, cond, users, pos, X0=None, t=None, neg_items=None, neg_users=None, masks=None,
                    apply=True, prior=None):
@@ -251,7 +262,7 @@ class RFGenerator(nn.Module):
         the slab gradient.  X0 / t / neg_* / masks: injected draws; apply=False skips the AdamW step.  prior: the
         backbone's user_prior, N x 64 fp32 of any row stride >= 64 (a constant of the step: v += (1 - t)^2 0.2 prior
         before the cosine term, rf_modules.py:460-465); None: no such term."""
-        N, U, B = self.N, self.U, users.numel()
+        N, U, B, D = self.N, self.U, users.numel(), self.D
         w = self._work(B)
         i32 = lambda a: None if a is None else a.to(self.dev).to(torch.int32).contiguous()  # noqa: E731
         neg_items, neg_users = i32(neg_items), i32(neg_users)
@@ -263,29 +274,29 @@ class RFGenerator(nn.Module):
             _lib.call("gmr_rf_rand", N, self.seed, self.step_ctr, SITE_T, ptr(w["t"]), stream())
         else:
             w["t"].copy_(t.reshape(N))
-        _lib.call("gmr_rf_interp", N, ptr(X1), X1.stride(0), ptr(w["X0"]), ptr(w["t"]), ptr(w["Xt"]), stream())
+        self._rf("gmr_rf_interp", N, ptr(X1), X1.stride(0), ptr(w["X0"]), ptr(w["t"]), ptr(w["Xt"]), stream())
         _lib.call("gmr_rf_time_embed", N, ptr(w["t"]), ptr(w["S"]), stream())
         V = self._net_fwd(w, w["Xt"], w["S"], cond, masks)
         if prior is None:
-            _lib.call("gmr_rf_head_fwd", N, ptr(V), ptr(w["Xt"]), ptr(X1), X1.stride(0), ptr(w["X0"]), ptr(w["t"]),
-                      GUIDANCE_SCALE, ptr(w["pred"]), ptr(w["rowparts"]), stream())
+            self._rf("gmr_rf_head_fwd", N, ptr(V), ptr(w["Xt"]), ptr(X1), X1.stride(0), ptr(w["X0"]), ptr(w["t"]),
+                     GUIDANCE_SCALE, ptr(w["pred"]), ptr(w["rowparts"]), stream())
         else:
             if prior.dtype != torch.float32 or tuple(prior.shape) != (N, D) or prior.stride(1) != 1:
                 raise ValueError(f"prior must be a {N} x {D} fp32 table with unit column stride")
-            _lib.call("gmr_rf_head_prior_fwd", N, ptr(V), ptr(w["Xt"]), ptr(X1), X1.stride(0), ptr(w["X0"]),
-                      ptr(w["t"]), ptr(prior), prior.stride(0), PRIOR_SCALE, GUIDANCE_SCALE, ptr(w["pred"]),
-                      ptr(w["rowparts"]), stream())
+            self._rf("gmr_rf_head_prior_fwd", N, ptr(V), ptr(w["Xt"]), ptr(X1), X1.stride(0), ptr(w["X0"]),
+                     ptr(w["t"]), ptr(prior), prior.stride(0), PRIOR_SCALE, GUIDANCE_SCALE, ptr(w["pred"]),
+                     ptr(w["rowparts"]), stream())
         # contrib rows [users | positive items] -> one sorted scatter into dpred (anchors repeat)
         coef = self.weight / B
         cp, cb = w["clparts"], w["contrib"]
         self.infonce(w["pred"], X1, 0, U, users, cp[:B], cb[:B], neg_users, SITE_NEG_USERS, coef)
         self.infonce(w["pred"], X1, U, self.I, pos, cp[B:2 * B], cb[B:2 * B], neg_items, SITE_NEG_ITEMS, coef)
-        _lib.call("gmr_rf_losses", N, ptr(w["rowparts"]), B, ptr(cp), self.weight, ptr(w["loss"]), stream())
+        self._rf("gmr_rf_losses", N, ptr(w["rowparts"]), B, ptr(cp), self.weight, ptr(w["loss"]), stream())
         plan = sort_plan((users, pos), w["ka"])
         K.zero_(w["dpred"])
         _lib.call("gmr_scatter_sorted_f32", plan.numel(), D, ptr(plan), ptr(cb), D, ptr(w["dpred"]), D, stream())
-        _lib.call("gmr_rf_head_bwd", N, ptr(V), ptr(X1), X1.stride(0), ptr(w["X0"]), ptr(w["t"]), ptr(w["dpred"]),
-                  ptr(w["dV"]), stream())
+        self._rf("gmr_rf_head_bwd", N, ptr(V), ptr(X1), X1.stride(0), ptr(w["X0"]), ptr(w["t"]), ptr(w["dpred"]),
+                 ptr(w["dV"]), stream())
         self.slab.zero_grad()
         self._net_bwd(w, w["Xt"], w["S"], cond)
         self.step_ctr += 1
@@ -308,7 +319,7 @@ class RFGenerator(nn.Module):
         (N x 64 fp32, any row stride that is a multiple of 4, not out's table): out = base + inference_mix_ratio *
         rows instead of the rows, the mix as the sampler's epilogue (gmr_rf_sample_mix, the ratio read from the
         device scalar _ratio) or, fused=False, composed from the same entry points as the other RF models' mix."""
-        N = cond.shape[0]
+        N, D = cond.shape[0], self.D
         n_steps = int(n_steps or self.sampling_steps)
         if z0 is None:
             z0 = torch.empty((N, D), dtype=torch.float32, device=self.dev)
@@ -322,19 +333,20 @@ class RFGenerator(nn.Module):
             if base.dtype != torch.float32 or tuple(base.shape) != (N, D) or base.stride(1) != 1:
                 raise ValueError(f"base must be a {N} x {D} fp32 table with unit column stride")
             if fused:
-                _lib.call("gmr_rf_sample_mix", N, H, self.C, self.L, n_steps, ptr(z0), z0.stride(0), ptr(cond),
-                          cond.stride(0), ptr(self.slab.data), ptr(base), base.stride(0), ptr(self._ratio), ptr(out),
-                          out.stride(0), stream())
+                self._rf("gmr_rf_sample_mix", N, H, self.C, self.L, n_steps, ptr(z0), z0.stride(0), ptr(cond),
+                         cond.stride(0), ptr(self.slab.data), ptr(base), base.stride(0), ptr(self._ratio), ptr(out),
+                         out.stride(0), stream(), at=2)
                 return out
             if not out.is_contiguous():
-                raise ValueError("the composed mix writes a contiguous N x 64 table")
+                raise ValueError(f"the composed mix writes a contiguous N x {D} table")
             gen = self._generate_composed(cond, z0, n_steps, torch.empty_like(out))
-            copy64(base, out)
+            for c0 in range(0, D, 64):
+                copy64(base[:, c0:c0 + 64], out[:, c0:c0 + 64])
             _lib.call("gmr_axpy_dev_f32", N * D, ptr(self._ratio), ptr(gen), ptr(out), stream())
             return out
         if fused:
-            _lib.call("gmr_rf_sample", N, H, self.C, self.L, n_steps, ptr(z0), z0.stride(0), ptr(cond),
-                      cond.stride(0), ptr(self.slab.data), ptr(out), out.stride(0), stream())
+            self._rf("gmr_rf_sample", N, H, self.C, self.L, n_steps, ptr(z0), z0.stride(0), ptr(cond),
+                     cond.stride(0), ptr(self.slab.data), ptr(out), out.stride(0), stream(), at=2)
             return out
         return self._generate_composed(cond, z0, n_steps, out)
 
@@ -342,7 +354,7 @@ class RFGenerator(nn.Module):
         """The same integration, one launch per layer (the training kernels with no masks); N must be self.N."""
         if cond.shape[0] != self.N:
             raise ValueError("the composed sampler runs on the generator's own N rows")
-        w = self._work(1)
+        w, D = self._work(1), self.D
         save, self.dropout = self.dropout, 0.0
         try:
             z = w["Xt"]
@@ -368,7 +380,8 @@ class RFBackbone:
     allocates no generator.  The model adds its buffers in __init__ (when use_rf), rf_step_inputs() -> (X1, cond,
     prior or None), the tables of the last backbone step the RF step trains on, and forward_embeddings(z0=None), its
     rule for mixing generate()'s rows into the evaluation tables once rf_warm().  rf_condition_dim() is the width of
-    cond: 64 per modality unless the model says otherwise."""
+    cond: 64 per modality unless the model says otherwise; rf_embedding_dim() the width of X1 and of the generated
+    rows: 64 unless the model says otherwise."""
 
     def __init__(self, config, dataloader):
         super().__init__(config, dataloader)
@@ -378,13 +391,17 @@ class RFBackbone:
             return
         check_config(config)
         self.rf_generator = RFGenerator(self.n_users, self.n_items, self.rf_condition_dim(), self.device,
-                                        seed=config_seed(config),
+                                        seed=config_seed(config), embedding_dim=self.rf_embedding_dim(),
                                         **{kw: _get(config, key, d) for kw, (key, d) in RF_CONFIG.items()})
         self._training_epoch = -1  # incremented to 0 by the first pre_epoch_processing
 
     def rf_condition_dim(self):
         """Columns of the condition table: one 64-wide block per modality."""
         return 64 * len(self.mods)
+
+    def rf_embedding_dim(self):
+        """Columns of the target table and of the generated rows."""
+        return D
 
     # ------------------------------------------------------------------ state
     def extra_state(self):

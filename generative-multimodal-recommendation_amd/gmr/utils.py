@@ -10,7 +10,8 @@ import torch
 _MODELS = {"DiffMM": "diffmm", "DiffRec": "diffrec", "VBPR": "vbpr", "GenRecV1": "genrecv1",
            "FREEDOM": "freedom", "RFFREEDOM": "rffreedom", "LD4MRec": "ld4mrec", "DDRM": "ddrm", "BM3": "bm3",
            "RFBM3": "rfbm3", "MGCN": "mgcn", "RFMGCN": "rfmgcn", "LATTICE": "lattice", "SMORE": "smore",
-           "RFSMORE": "rfsmore", "LGMRec": "lgmrec", "RFLGMRec": "rflgmrec", "GRCN": "grcn"}
+           "RFSMORE": "rfsmore", "LGMRec": "lgmrec", "RFLGMRec": "rflgmrec", "GRCN": "grcn",
+           "RFGRCN": "rfgrcn"}
 
 
 def get_local_time():

@@ -891,6 +891,55 @@ int gmr_rf_infonce_sampled_fwd_bwd(int32_t B, int64_t n, const float* pred, int6
                                    int64_t ldt, int64_t row_off, const int32_t* idx, int32_t n_neg, const int32_t* neg,
                                    uint64_t seed, uint64_t step, uint64_t site, float inv_temp, float coef,
                                    double* parts, float* contrib, int64_t ldc, void* stream);
+/* ---- the generator at row width DW (the _w entry points).  The concat-fusion backbones generate rows as wide as
+ * their conditions: embedding_dim DW with condition_dim C, (DW, C) in {(64, 64), (64, 128), (64, 192), (128, 128),
+ * (192, 192)}.  The packed parameters are the same order with input_proj W 128 x DW and output_proj {W DW x 128,
+ * b DW}; the sinusoidal time embedding stays 64 wide.  Every _w entry at DW = 64 is the entry without the suffix,
+ * bit for bit (one kernel behind both names); every table that was N x 64 is N x DW, with the same stride and
+ * alignment rules.  Any other width: GMR_ERR_ARG (gmr_rf_param_floats_w: -1). */
+int64_t gmr_rf_param_floats_w(int32_t DW, int32_t C, int32_t L);
+/* gmr_rf_sample / gmr_rf_sample_mix with z0, out and base N x DW.  A workgroup still owns 32 rows; its z tile is
+ * 32 x (DW + 4) floats and the output projection runs over DW / 32 column tiles shared among the four waves, every
+ * element's sum in one fixed order.  The wide instantiations take 66.75 KB (DW = 128) / 74.75 KB (DW = 192) of
+ * dynamic LDS, so two workgroups share a CU. */
+int gmr_rf_sample_w(int64_t N, int32_t hidden, int32_t DW, int32_t C, int32_t L, int32_t n_steps, const float* z0,
+                    int64_t ldz, const float* cond, int64_t ldc, const float* params, float* out, int64_t ldo,
+                    void* stream);
+int gmr_rf_sample_mix_w(int64_t N, int32_t hidden, int32_t DW, int32_t C, int32_t L, int32_t n_steps, const float* z0,
+                        int64_t ldz, const float* cond, int64_t ldc, const float* params, const float* base,
+                        int64_t ldb, const float* ratio, float* out, int64_t ldo, void* stream);
+/* The row kernels over N x DW tables, DW in {64, 128, 192}: X1 (ld1) and prior (ldp) keep row strides of their own,
+ * the rest are contiguous.  The head is one wave per row with DW / 64 columns per lane; norms, dots and the fp64
+ * squared error run over the whole row.  gmr_rf_head_bwd_w and gmr_rf_losses_w divide by DW N. */
+int gmr_rf_interp_w(int64_t N, int32_t DW, const float* X1, int64_t ld1, const float* X0, const float* t, float* Xt,
+                    void* stream);
+int gmr_rf_head_fwd_w(int64_t N, int32_t DW, float* V, const float* Xt, const float* X1, int64_t ld1, const float* X0,
+                      const float* t, float guidance_scale, float* pred, double* row_parts, void* stream);
+int gmr_rf_head_prior_fwd_w(int64_t N, int32_t DW, float* V, const float* Xt, const float* X1, int64_t ld1,
+                            const float* X0, const float* t, const float* prior, int64_t ldp, float prior_scale,
+                            float cos_scale, float* pred, double* row_parts, void* stream);
+int gmr_rf_head_bwd_w(int64_t N, int32_t DW, const float* V, const float* X1, int64_t ld1, const float* X0,
+                      const float* t, const float* dpred, float* dV, void* stream);
+int gmr_rf_losses_w(int64_t N, int32_t DW, const double* row_parts, int64_t B, const double* cl_parts, float weight,
+                    float* out3, void* stream);
+/* gmr_rf_infonce_sampled_fwd_bwd over DW-wide rows: a 16-lane group holds a row as DW / 64 float4 per lane, four
+ * negatives per wave; the Philox indexing (so the drawn indices for one key are those of every width), the collision
+ * rule and the per-column normalisation over the anchor's negatives are unchanged.  contrib rows are DW wide. */
+int gmr_rf_infonce_sampled_fwd_bwd_w(int32_t B, int64_t n, int32_t DW, const float* pred, int64_t ldp,
+                                     const float* target, int64_t ldt, int64_t row_off, const int32_t* idx,
+                                     int32_t n_neg, const int32_t* neg, uint64_t seed, uint64_t step, uint64_t site,
+                                     float inv_temp, float coef, double* parts, float* contrib, int64_t ldc,
+                                     void* stream);
+/* RFGRCN's prior (models/rfgrcn.py:171-190): prior[r, :W] = src[r, :W] - the column means of r's segment (the U user
+ * rows, then the I item rows), W in {64, 128, 192}; src ((U + I) x W, lds) and prior (ldp) may be column blocks of
+ * wider tables, nothing outside the block is written.  Centring every 64-wide block on its own, as the reference
+ * does, is centring the whole row.  The grid, the block partials and the fixed-order means are gmr_rf_view_prior's at
+ * row width W: no float atomics, two runs are bit-identical.  1 <= U, I <= 2^31 - 128.  ws:
+ * gmr_rf_center_segments_ws_floats(U, I, W) floats (-1 outside the range).  All pointers 16-byte aligned, strides
+ * multiples of 4 floats. */
+int64_t gmr_rf_center_segments_ws_floats(int64_t U, int64_t I, int32_t W);
+int gmr_rf_center_segments(int64_t U, int64_t I, int32_t W, const float* src, int64_t lds, float* prior, int64_t ldp,
+                           float* ws, void* stream);
 /* torch.optim.AdamW: p <- p * decay_factor (= 1 - lr wd) first, then gmr_adam_f32's update without its L2 term */
 int gmr_adamw_f32(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
                   float beta2, float eps, float decay_factor, float step_size, float bias_correction2_sqrt,
